@@ -10,6 +10,10 @@ all-gather of the decoded dmsg buffers (BASELINE config 5).  Weak scaling: each 
 Prints ONE JSON line on rank 0 (contract in the task statement); see DESIGN.md §Measurement.
 The mixed step runs as ONE kernel (k_step, sdx_demod_step: MU, then MS, then MC tiles) beside the
 next step's grouping on a low-priority side stream (sdx_group_step).
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the line.  ``--full`` adds what takes
+runs of its own (per-kernel attribution passes, roofline / issue figures, the CPU baseline);
+``--dump-outputs DIR`` writes the last timed step's results as .npy files.
 """
 from __future__ import annotations
 
@@ -34,8 +38,15 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--msgs", type=int, default=1_000_000, help="messages per rank (1/3 MU, 1/3 MS, 1/3 MC)")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU-baseline leg")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline does not need: each kind's kernel and the "
+                         "grouping alone (untimed attribution passes), the roofline / issue figures and the CPU "
+                         "baseline (a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, < 64 MB in "
+                         "all; see dump_outputs): same arguments, same inputs, so two builds compare file by file")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU-baseline leg (--full)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU-baseline leg")
     ap.add_argument("--exchange", action="store_true",
                     help="run the N > 1 exchange (RCCL process group, overlapped all-gather) even at world size 1")
     ap.add_argument("--kind", default="mixed", choices=("mixed", "MU", "MS", "MC"),
@@ -232,6 +243,87 @@ def attribute_alone(torch, eng, stream, kinds, bds, outs, gbufs, corp, mrec_kind
                 ts.append(e0.elapsed_time(e1) * 1e-3)
             res[k] = float(np.median(ts))
     return res
+
+
+DUMP_BUDGET = 60_000_000   # bytes of array data --dump-outputs writes in all (the limit is 64 MB)
+DUMP_SEED = 20240
+CSUM_MOD = 16777213        # a prime below 2^24: every checksum is exact in float32
+
+
+def _ranges(begin, count):
+    """The concatenation of arange(begin[i], begin[i] + count[i]) over i."""
+    start = np.cumsum(count) - count
+    return np.repeat(begin - start, count) + np.arange(int(count.sum()), dtype=np.int64)
+
+
+def _segment_sums(values, count):
+    """Sums of consecutive runs of ``values`` of the lengths ``count`` (a run may be empty)."""
+    c = np.concatenate([[0], np.cumsum(values, dtype=np.int64)])
+    start = np.cumsum(count) - count
+    return c[start + count] - c[start]
+
+
+def _payload_checksums(heap, off, length, chunk=1 << 18):
+    """Per record sum((1 + i mod 251) * byte[i]) mod CSUM_MOD over its payload bytes."""
+    out = np.zeros(len(off), np.int64)
+    for a in range(0, len(off), chunk):   # chunks bound the per-byte index arrays
+        o, ln = off[a: a + chunk], length[a: a + chunk]
+        within = _ranges(np.zeros(len(ln), np.int64), ln)
+        out[a: a + chunk] = _segment_sums(heap[np.repeat(o, ln) + within].astype(np.int64) * (within % 251 + 1), ln)
+    return out % CSUM_MOD
+
+
+def dump_outputs(dirname, prefix, fetched):
+    """--dump-outputs: what a caller of the timed path receives for the last timed step -- per kind the
+    (desc, rec, heap) of Engine.fetch -- in canonical form (a message's records sit wherever the kernel's
+    atomic cursor put them; here they follow message order) as float arrays:
+      <kind>_msgs.npy     f64 [m]    the dumped messages' indices (all of them while everything fits the
+                                     budget, else a seeded sample, ascending)
+      <kind>_desc.npy     f32 [m,3]  n_rec, status, raise_kind per dumped message
+      <kind>_rec.npy      f32 [r,4]  proto, bit_length, payload_len, payload checksum per record of those
+                                     messages, message by message in the kernel's (reference) order
+      <kind>_payload_msgs.npy f64 [p], <kind>_payload.npy f32 [b]   a seeded sample of the dumped messages and
+                                     the payload bytes of their records, concatenated in the same order
+    Returns the bytes written."""
+    from pysignalduino_amd import runtime
+    os.makedirs(dirname, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    norm = {}
+    for k, (desc, rec, heap) in fetched.items():   # records only of messages that completed, inside what was written
+        nr = np.where(desc["status"] == runtime.ST_OK, desc["n_rec"], 0).astype(np.int64)
+        rb = desc["rec_begin"].astype(np.int64)
+        nr[rb + nr > len(rec)] = 0
+        norm[k] = (nr, rb)
+    cost = sum(20 * len(nr) + 16 * int(nr.sum()) for nr, _ in norm.values())
+    frac = min(1.0, 0.85 * DUMP_BUDGET / max(cost, 1))
+    pay_cap = int(0.15 * DUMP_BUDGET / 4 / len(fetched))   # payload bytes per kind (one float32 each)
+    written = 0
+
+    def save(name, arr):
+        nonlocal written
+        np.save(os.path.join(dirname, f"{prefix}{name}.npy"), arr)
+        written += arr.nbytes
+
+    for k, (desc, rec, heap) in fetched.items():
+        nr, rb = norm[k]
+        n = len(desc)
+        keep = np.arange(n) if frac >= 1.0 else np.sort(rng.permutation(n)[: int(n * frac)])
+        nrk = nr[keep]
+        r = rec[_ranges(rb[keep], nrk)]
+        po, pl = r["payload_off"].astype(np.int64), r["payload_len"].astype(np.int64)
+        pl_in = np.where(po + pl <= len(heap), pl, 0)   # a payload past the written heap counts no bytes
+        save(f"{k}_msgs", keep.astype(np.float64))
+        save(f"{k}_desc", np.stack([nrk, desc["status"][keep], desc["raise_kind"][keep]], axis=1).astype(np.float32))
+        save(f"{k}_rec", np.stack([r["proto"], r["bit_length"], pl, _payload_checksums(heap, po, pl_in)],
+                                  axis=1).astype(np.float32))
+        order = rng.permutation(len(keep))
+        per_msg = _segment_sums(pl_in, nrk)
+        sel = np.sort(order[: int(np.searchsorted(np.cumsum(per_msg[order]), pay_cap, side="right"))])
+        recs = _ranges((np.cumsum(nrk) - nrk)[sel], nrk[sel])
+        save(f"{k}_payload_msgs", keep[sel].astype(np.float64))
+        save(f"{k}_payload", heap[_ranges(po[recs], pl_in[recs])].astype(np.float32))
+    assert written <= 64 * 1000 * 1000, written
+    return written
 
 
 # the committed per-kernel PMC summary the line's roofline.traffic / issue come from: a tracked file that
@@ -553,89 +645,109 @@ def main():
     dt = float(tt.item())
     total_msgs = sum(per.values()) * world * args.steps
     value = total_msgs / dt
-
-    # roofline of the dominant kernel: SURVEY §8(d) algorithmic bytes / its HIP-event time
-    kt = {k: float(np.mean(v)) for k, v in ktimes.items()}
+    kt = {k: float(np.mean(v)) for k, v in ktimes.items()}   # the timed steps' own HIP events
     bds, corp = bdl[(j - 1) % nb], corps[(j - 1) % nb]   # the last timed step's batch (its order: parity j-1)
-    if fused:   # each kind's kernel alone (untimed attribution pass): its own roofline entry
-        kt_step = kt["step"]
-        kt = attribute_alone(torch, eng, stream, kinds, bds, outs[(j - 1) % nslot], gbufs, corp, mrec_kinds,
-                             (j - 1) % 2)
-    # the grouping's own time (one step's groupings alone on the launch stream, untimed): group_ms is
-    # the side stream's wall time beside the step's kernel, mostly waiting for CU slots
-    g_alone = None
-    if gkinds:
-        gts = []
-        with torch.cuda.stream(stream):
-            for _ in range(5):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record(stream)
-                if gkinds == ["MU", "MS"] and not args.group_separate:
-                    eng.group_step(bds["MU"], bds["MS"], gbufs["MU"][0], gbufs["MS"][0])
-                else:
-                    for k in gkinds:
-                        eng.group(runtime.KIND_MU if k == "MU" else runtime.KIND_MS, bds[k], bufs=gbufs[k][0])
-                e1.record(stream)
-                stream.synchronize()
-                gts.append(e0.elapsed_time(e1) * 1e-3)
-        g_alone = float(np.median(gts))
-    dom = max(kt, key=kt.get)
-    # every kind's launch against the same HBM roofline: its algorithmic bytes (the
-    # outputs of the last step) / its HIP-event time -- with the fused step each kernel timed alone in
-    # the attribution pass; with --no-fuse MS and MC run side by side after MU (MC on its own stream,
-    # started at MU's end), so their times include that sharing; --kind MU|MS|MC times each kernel alone
-    kern_tag = {"MU": "k_pulses<MU>", "MS": "k_pulses<MS>", "MC": "k_mc"}
-    kernels = {}
-    for k in kinds:
-        ok_ = outs[(j - 1) % nslot][k]
-        ck = ok_["cursor"].cpu().numpy().astype(np.int64)
-        rk = ok_["rec"][: int(ck[0]) * RES_DT.itemsize].cpu().numpy().view(RES_DT)
-        ak = alg_bytes(k, bds[k], rk)
-        kernels[k] = {"kernel": kern_tag[k], "alg_bytes_per_launch": ak, "results_per_launch": int(ck[0]),
-                      "ms": 1e3 * kt[k], "achieved_GBps": ak / kt[k] / 1e9, "frac": ak / kt[k] / HBM_PEAK,
-                      "shares_gpu_with": ("MC" if k == "MS" else "MS") if mc_beside_ms and k in ("MS", "MC") and not fused
-                      else None}
+    dumped = None
+    if args.dump_outputs:   # before --full's attribution passes write the same buffers again
+        dumped = dump_outputs(args.dump_outputs, f"rank{rank}_" if world > 1 else "",
+                              {k: eng.fetch(outs[(j - 1) % nslot][k]) for k in kinds})
+
+    def full_figures():
+        """--full: the line's fields that take launches of their own or describe single kernels."""
+        # roofline of the dominant kernel: SURVEY §8(d) algorithmic bytes / its HIP-event time
+        ka = kt
+        if fused:   # each kind's kernel alone (untimed attribution pass): its own roofline entry
+            kt_step = kt["step"]
+            ka = attribute_alone(torch, eng, stream, kinds, bds, outs[(j - 1) % nslot], gbufs, corp, mrec_kinds,
+                                 (j - 1) % 2)
+        # the grouping's own time (one step's groupings alone on the launch stream, untimed): group_ms is
+        # the side stream's wall time beside the step's kernel, mostly waiting for CU slots
+        g_alone = None
+        if gkinds:
+            gts = []
+            with torch.cuda.stream(stream):
+                for _ in range(5):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(stream)
+                    if gkinds == ["MU", "MS"] and not args.group_separate:
+                        eng.group_step(bds["MU"], bds["MS"], gbufs["MU"][0], gbufs["MS"][0])
+                    else:
+                        for k in gkinds:
+                            eng.group(runtime.KIND_MU if k == "MU" else runtime.KIND_MS, bds[k], bufs=gbufs[k][0])
+                    e1.record(stream)
+                    stream.synchronize()
+                    gts.append(e0.elapsed_time(e1) * 1e-3)
+            g_alone = float(np.median(gts))
+        dom = max(ka, key=ka.get)
+        # every kind's launch against the same HBM roofline (VERDICT r04 #5): its algorithmic bytes (the
+        # outputs of the last step) / its HIP-event time -- with the fused step each kernel timed alone in
+        # the attribution pass; with --no-fuse MS and MC run side by side after MU (MC on its own stream,
+        # started at MU's end), so their times include that sharing; --kind MU|MS|MC times each kernel alone
+        kern_tag = {"MU": "k_pulses<MU>", "MS": "k_pulses<MS>", "MC": "k_mc"}
+        kernels = {}
+        for k in kinds:
+            ok_ = outs[(j - 1) % nslot][k]
+            ck = ok_["cursor"].cpu().numpy().astype(np.int64)
+            rk = ok_["rec"][: int(ck[0]) * RES_DT.itemsize].cpu().numpy().view(RES_DT)
+            ak = alg_bytes(k, bds[k], rk)
+            kernels[k] = {"kernel": kern_tag[k], "alg_bytes_per_launch": ak, "results_per_launch": int(ck[0]),
+                          "ms": 1e3 * ka[k], "achieved_GBps": ak / ka[k] / 1e9, "frac": ak / ka[k] / HBM_PEAK,
+                          "shares_gpu_with": ("MC" if k == "MS" else "MS")
+                          if mc_beside_ms and k in ("MS", "MC") and not fused else None}
+            if fused:
+                kernels[k]["timed"] = "alone, untimed attribution pass after the timed loop (the timed step runs k_step)"
+        step_roof = None
         if fused:
-            kernels[k]["timed"] = "alone, untimed attribution pass after the timed loop (the timed step runs k_step)"
-    step_roof = None
-    if fused:
-        salg = sum(kernels[k]["alg_bytes_per_launch"] for k in kinds)
-        step_roof = {"kernel": "k_step (MU + MS + MC tiles, one launch)", "alg_bytes_per_launch": salg,
-                     "ms": 1e3 * kt_step, "achieved_GBps": salg / kt_step / 1e9, "frac": salg / kt_step / HBM_PEAK}
-    o = outs[(j - 1) % nslot][dom]
-    cur = o["cursor"].cpu().numpy().astype(np.int64)
-    alg = kernels[dom]["alg_bytes_per_launch"]
-    n = bds[dom]["n"]
-    layout = (int(bds[dom]["lengths"].sum()) + n * ((8 + 4 + 4 + 1) if dom == "MC" else
-                                                    (8 + 1 + 10 + 80 + (2 if dom == "MS" else 0)))
-              + n * runtime.DESC_DT.itemsize + int(cur[0]) * RES_DT.itemsize + int(cur[1]) + len(bk.blob))
-    achieved = alg / kt[dom]
-    traffic = issue = traffic_src = None
-    tag = f"k_pulses<{dom}>" if dom != "MC" else "k_mc"
-    t_dom = kt[dom]
-    if fused:   # the timed region's one kernel: k_step over the whole step's algorithmic bytes
-        tag, alg, t_dom = "k_step", step_roof["alg_bytes_per_launch"], kt_step
-        achieved = alg / kt_step
-        layout = None
-    tpath = latest_pmc()
-    if tpath and args.corpus == "bench":
-        with open(tpath) as fh:
-            tj = json.load(fh)
-        cfg = tj.get("_config", {})
-        if cfg.get("msgs_per_gpu") == args.msgs and cfg.get("kind", "mixed") == args.kind and \
-                tj.get(tag, {}).get("traffic_bytes"):
-            traffic = float(tj[tag]["traffic_bytes"])
-            src = tj.get("_source", {})
-            loaded = runtime.load_library().sdx_source_hash().decode()
-            traffic_src = {"pmc": os.path.relpath(tpath, REPO), "commit": src.get("commit"),
-                           "sdx_source_hash": src.get("sdx_source_hash"),
-                           "same_kernels_as_this_run": src.get("sdx_source_hash") == loaded,
-                           "profiles": src.get("profiles"),
-                           "fetch_bytes": 2 * 1024 * float(tj[tag]["fetch_size_kib"]),
-                           "write_bytes": 1024 * float(tj[tag]["write_size_kib"]),
-                           "calibration": "profiles/r05/calib/calib_traffic.json (FETCH_SIZE x 2 holds for every "
-                                          "vector load width this kernel uses; scalar loads count exactly)"}
-            issue = issue_view(tj[tag], t_dom)
+            salg = sum(kernels[k]["alg_bytes_per_launch"] for k in kinds)
+            step_roof = {"kernel": "k_step (MU + MS + MC tiles, one launch)", "alg_bytes_per_launch": salg,
+                         "ms": 1e3 * kt_step, "achieved_GBps": salg / kt_step / 1e9, "frac": salg / kt_step / HBM_PEAK}
+        o = outs[(j - 1) % nslot][dom]
+        cur = o["cursor"].cpu().numpy().astype(np.int64)
+        alg = kernels[dom]["alg_bytes_per_launch"]
+        n = bds[dom]["n"]
+        layout = (int(bds[dom]["lengths"].sum()) + n * ((8 + 4 + 4 + 1) if dom == "MC" else
+                                                        (8 + 1 + 10 + 80 + (2 if dom == "MS" else 0)))
+                  + n * runtime.DESC_DT.itemsize + int(cur[0]) * RES_DT.itemsize + int(cur[1]) + len(bk.blob))
+        achieved = alg / ka[dom]
+        traffic = issue = traffic_src = None
+        tag = f"k_pulses<{dom}>" if dom != "MC" else "k_mc"
+        t_dom = ka[dom]
+        if fused:   # the timed region's one kernel: k_step over the whole step's algorithmic bytes
+            tag, alg, t_dom = "k_step", step_roof["alg_bytes_per_launch"], kt_step
+            achieved = alg / kt_step
+            layout = None
+        tpath = latest_pmc()
+        if tpath and args.corpus == "bench":
+            with open(tpath) as fh:
+                tj = json.load(fh)
+            cfg = tj.get("_config", {})
+            if cfg.get("msgs_per_gpu") == args.msgs and cfg.get("kind", "mixed") == args.kind and \
+                    tj.get(tag, {}).get("traffic_bytes"):
+                traffic = float(tj[tag]["traffic_bytes"])
+                src = tj.get("_source", {})
+                loaded = runtime.load_library().sdx_source_hash().decode()
+                traffic_src = {"pmc": os.path.relpath(tpath, REPO), "commit": src.get("commit"),
+                               "sdx_source_hash": src.get("sdx_source_hash"),
+                               "same_kernels_as_this_run": src.get("sdx_source_hash") == loaded,
+                               "profiles": src.get("profiles"),
+                               "fetch_bytes": 2 * 1024 * float(tj[tag]["fetch_size_kib"]),
+                               "write_bytes": 1024 * float(tj[tag]["write_size_kib"]),
+                               "calibration": "profiles/r05/calib/calib_traffic.json (FETCH_SIZE x 2 holds for every "
+                                              "vector load width this kernel uses; scalar loads count exactly)"}
+                issue = issue_view(tj[tag], t_dom)
+        return {
+            "per_kernel_ms": {**({"step": 1e3 * kt_step} if fused else {}), **{k: 1e3 * v for k, v in ka.items()}},
+            "group_alone_ms": None if g_alone is None else 1e3 * g_alone,   # the step's groupings alone, untimed
+            "per_type_msgs_per_s": {k: per[k] / ka[k] for k in kinds},
+            "roofline": {"bound": "hbm", "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                         "frac": achieved / HBM_PEAK, "traffic": traffic, "kernel": tag,
+                         "alg_bytes_per_launch": alg, "layout_bytes_per_launch": layout,
+                         "results_per_launch": (sum(k_["results_per_launch"] for k_ in kernels.values()) if fused
+                                                else int(cur[0])),
+                         "issue": issue, "traffic_source": traffic_src,
+                         "per_kernel": kernels, **({"step": step_roof} if fused else {})},
+        }
+
     wl = {"mixed": "mixed MU/MS/MC stream, 1/3 each per rank: MU 256-pulse messages x 129-id MU bank, MS sync+bits x "
                    "66-id MS bank (clock x U(0.6,1.4)), MC frames x 12 clockrange ids ('fixed' chain)",
           "MU": "config 2: 256-pulse MU messages x 129-id MU bank",
@@ -659,29 +771,25 @@ def main():
                    "streams": ("one kernel (k_step: MU, then MS, then MC tiles)" if fused else
                                "one per kind" if args.concurrent and len(kinds) > 1 else
                                "MU, then MS beside MC" if mc_beside_ms else "serial")},
-        "per_kernel_ms": {**({"step": 1e3 * kt_step} if fused else {}), **{k: 1e3 * v for k, v in kt.items()}},
+        "per_kernel_ms": {k: 1e3 * v for k, v in kt.items()},   # the timed steps' own HIP events
         "group_ms": 1e3 * gtime,   # sdx_group_pulses of all kinds per step (side stream, one step ahead)
-        "group_alone_ms": None if g_alone is None else 1e3 * g_alone,   # the same groupings alone, untimed
-        "per_type_msgs_per_s": {k: per[k] / kt[k] for k in kinds},
-        "roofline": {"bound": "hbm", "achieved": achieved / 1e9, "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK, "traffic": traffic, "kernel": tag,
-                     "alg_bytes_per_launch": alg, "layout_bytes_per_launch": layout,
-                     "results_per_launch": sum(k_["results_per_launch"] for k_ in kernels.values()) if fused else int(cur[0]),
-                     "issue": issue, "traffic_source": traffic_src,
-                     "per_kernel": kernels, **({"step": step_roof} if fused else {})},
     }
+    if dumped is not None:
+        res["dump_outputs"] = {"dir": args.dump_outputs, "bytes": dumped}
+    if args.full:
+        res.update(full_figures())
     if exch is not None and exch.bytes_sent:
-        nb = exch.bytes_sent[-args.steps:]
+        sb = exch.bytes_sent[-args.steps:]
         wb = exch.wire_bytes[-args.steps:]
         res["exchange"] = {"format": "wire v3 (include/sdx.h): 4 B/message + 8 B/record + payloads "
                                      + ("raw" if args.raw_wire else "(preamble + hex + postamble as packed digits)"),
                            "scheduling": args.xchg,
                            "branch": "pipelined" if exch.pipelined else "sync",
-                           "send_bytes_per_rank_per_step": float(np.mean(nb)),
+                           "send_bytes_per_rank_per_step": float(np.mean(sb)),
                            "wire_bytes_per_rank_per_step": float(np.mean(wb)),
                            "payload_bytes_per_rank_per_step": float(np.mean(exch.payload_bytes[-args.steps:])),
                            "payload_wire_bytes_per_rank_per_step": float(np.mean(exch.heap_wire_bytes[-args.steps:])),
-                           "recv_bytes_per_rank_per_step": float(np.mean(nb)) * world,
+                           "recv_bytes_per_rank_per_step": float(np.mean(sb)) * world,
                            "reruns": exch.reruns}
     if ovf:   # dense corpus: messages whose results did not fit the on-chip staging (the product re-runs them)
         res["overflow"] = {}
@@ -689,7 +797,7 @@ def main():
             d = outs[(j - 1) % nslot][k]["desc"][: corp[k].n * runtime.DESC_DT.itemsize].cpu().numpy().view(runtime.DESC_DT)
             res["overflow"][k] = {"flags": ovf[k], "tile_msgs": int((d["status"] == runtime.ST_OVF_TILE).sum()),
                                   "out_msgs": int((d["status"] == runtime.ST_OVF_OUT).sum())}
-    if rank == 0 and not args.no_cpu:
+    if args.full and rank == 0 and not args.no_cpu:
         res["cpu_baseline"] = cpu_baseline(corps[0].get("MU"), corps[0].get("MS"), corps[0].get("MC"), args.cpu_seconds,
                                            kinds)
     if rank == 0:

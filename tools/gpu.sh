@@ -8,18 +8,18 @@
 #   warm                 import torch + device name (a fresh box pages torch in: 1-2 min)  -> OUT/warm.log
 #   tests[=PYTEST_K]     the whole -m gpu suite (or -k PYTEST_K)            -> OUT/tests*.txt
 #   smoke                __graft_entry__.smoke()                           -> OUT/smoke.log
-#   bench[=ARGS]         python bench.py ARGS (',' separates arguments)    -> OUT/bench_<n>.log
-#   benchcpu             bench.py with the cpu_baseline leg                -> OUT/bench_cpu.log
+#   bench[=ARGS]         python bench.py --full --no-cpu ARGS (',' separates arguments) -> OUT/bench_<n>.log
+#   benchcpu             bench.py --full (with the cpu_baseline leg)       -> OUT/bench_cpu.log
 #   lines[=ARGS]         tools/bench_lines.py --no-cpu ARGS                -> OUT/lines_<n>.log
 #   e2e[=ARGS]           tools/bench_lines_e2e.py --check ARGS             -> OUT/e2e_<n>.log
 #   kt                   rocprofv3 --kernel-trace --stats of bench.py      -> OUT/kt_bench/
 #   ktlines              the same for tools/bench_lines.py                 -> OUT/kt_lines/
 #   ktpy=SCRIPT[,ARGS]   the same for python3 SCRIPT ARGS                  -> OUT/kt_<n>/
 #   ktpyenv=VAR=val,SCRIPT[,ARGS]  the same with VAR=val in the environment -> OUT/kt_<n>/
-#   ktx[=ARGS]           the same for bench.py --no-cpu ARGS (',' separates) -> OUT/ktx_<n>/
+#   ktx[=ARGS]           the same for bench.py --full --no-cpu ARGS (',' separates) -> OUT/ktx_<n>/
 #   pmc[=PASSES]         tools/pmc.sh (default sq1,sq2,fetch,write)        -> OUT/pmc/, OUT/pmc_traffic.json
 #   time=V1,V2           tools/time_mu.py for in-tree libsdx + variants V (pysignalduino_amd/_lib/ab/libsdx_V.so), 2 rounds
-#   env=E1,E2            bench.py --no-cpu under env settings E (VAR=value), 2 rounds
+#   env=E1,E2            bench.py --full --no-cpu under env settings E (VAR=value), 2 rounds
 #   py=SCRIPT[,ARGS]     python SCRIPT ARGS (a tools/ measurement)          -> OUT/py_<n>.log
 #   benchenv=VAR=val[,ARGS]  bench.py ARGS with VAR=val in the environment -> OUT/bench_<n>.log
 #   pyenv=VAR=val,SCRIPT[,ARGS]  python SCRIPT ARGS with VAR=val in the environment -> OUT/pyenv_<n>.log
@@ -60,18 +60,18 @@ for st in "$@"; do
       else run 900 "$O/tests.txt" python -u -m pytest tests -m gpu -x -v --timeout 150 --timeout-method thread; fi
       tail -1 "$O"/tests*.txt | tail -1 ;;
     smoke) run 240 "$O/smoke.log" python -c "import __graft_entry__ as g; g.smoke()"; tail -1 "$O/smoke.log" ;;
-    bench) run 240 "$O/bench_$n.log" python bench.py --no-cpu $args; echo "bench $arg: $(tail -1 "$O/bench_$n.log" | summ)" ;;
-    benchcpu) run 360 "$O/bench_cpu.log" python bench.py; tail -1 "$O/bench_cpu.log" | cut -c1-400 ;;
+    bench) run 240 "$O/bench_$n.log" python bench.py --full --no-cpu $args; echo "bench $arg: $(tail -1 "$O/bench_$n.log" | summ)" ;;
+    benchcpu) run 360 "$O/bench_cpu.log" python bench.py --full; tail -1 "$O/bench_cpu.log" | cut -c1-400 ;;
     lines) run 300 "$O/lines_$n.log" python tools/bench_lines.py --no-cpu $args; echo "lines $arg: $(tail -1 "$O/lines_$n.log" | cut -c1-300)" ;;
     e2e) run 400 "$O/e2e_$n.log" python -u tools/bench_lines_e2e.py --check $args; echo "e2e $arg: $(tail -1 "$O/e2e_$n.log" | cut -c1-400)" ;;
-    kt) run 300 "$O/kt_bench.log" rocprofv3 --kernel-trace --stats -d "$O/kt_bench" -o b --output-format csv -- python3 bench.py --no-cpu
+    kt) run 300 "$O/kt_bench.log" rocprofv3 --kernel-trace --stats -d "$O/kt_bench" -o b --output-format csv -- python3 bench.py --full --no-cpu
         echo "kt: $(tail -1 "$O/kt_bench.log" | summ)" ;;
     ktpy) run 300 "$O/ktpy_$n.log" rocprofv3 --kernel-trace --stats -d "$O/kt_$n" -o k --output-format csv -- python3 $args
         echo "ktpy $arg: $(tail -1 "$O/ktpy_$n.log" | cut -c1-300)" ;;
     ktpyenv) e=${args%% *}; rest=${args#* }
       run 300 "$O/ktpyenv_$n.log" env "$e" rocprofv3 --kernel-trace --stats -d "$O/kt_$n" -o k --output-format csv -- python3 $rest
       echo "ktpyenv $arg: $(tail -3 "$O/ktpyenv_$n.log" | cut -c1-300)" ;;
-    ktx) run 300 "$O/ktx_$n.log" rocprofv3 --kernel-trace --stats -d "$O/ktx_$n" -o b --output-format csv -- python3 bench.py --no-cpu $args
+    ktx) run 300 "$O/ktx_$n.log" rocprofv3 --kernel-trace --stats -d "$O/ktx_$n" -o b --output-format csv -- python3 bench.py --full --no-cpu $args
         echo "ktx $arg: $(tail -1 "$O/ktx_$n.log" | summ)" ;;
     ktlines) run 300 "$O/kt_lines.log" rocprofv3 --kernel-trace --stats -d "$O/kt_lines" -o l --output-format csv -- python3 tools/bench_lines.py --no-cpu
         echo "ktlines: $(tail -1 "$O/kt_lines.log" | cut -c1-200)" ;;
@@ -86,12 +86,12 @@ for st in "$@"; do
     env)
       for r in 1 2; do for e in $args; do
         tag=$(echo "$e" | tr '=/ ' '___')
-        run 240 "$O/env_${tag}_$r.log" env "$e" python bench.py --no-cpu
+        run 240 "$O/env_${tag}_$r.log" env "$e" python bench.py --full --no-cpu
         echo "$e $r: $(tail -1 "$O/env_${tag}_$r.log" | summ)"
       done; done ;;
     py) run 600 "$O/py_$n.log" python -u $args; echo "py $arg: $(tail -3 "$O/py_$n.log" | cut -c1-400)" ;;
     benchenv) e=${args%% *}; rest=${args#* }; [ "$rest" = "$e" ] && rest=""
-      run 240 "$O/bench_$n.log" env "$e" python bench.py --no-cpu $rest
+      run 240 "$O/bench_$n.log" env "$e" python bench.py --full --no-cpu $rest
       echo "bench $arg: $(tail -1 "$O/bench_$n.log" | summ)" ;;
     pyenv) e=${args%% *}; rest=${args#* }
       run 600 "$O/pyenv_$n.log" env "$e" python -u $rest
@@ -106,7 +106,7 @@ for st in "$@"; do
       grep -E "^(FAILED|ERROR)" "$O/testlib_$n.txt" | head -20 || true
       case $rc in 124|134|137|139) echo "tests stopped ($rc): no further GPU steps"; exit 1 ;; esac ;;
     benchlib) v=${args%% *}; rest=${args#* }; [ "$rest" = "$v" ] && rest=""
-      SDX_LIB=pysignalduino_amd/_lib/ab/libsdx_$v.so run 240 "$O/bench_$n.log" python bench.py --no-cpu $rest
+      SDX_LIB=pysignalduino_amd/_lib/ab/libsdx_$v.so run 240 "$O/bench_$n.log" python bench.py --full --no-cpu $rest
       echo "benchlib $arg: $(tail -1 "$O/bench_$n.log" | summ)" ;;
     *) echo "unknown step $st"; exit 2 ;;
   esac

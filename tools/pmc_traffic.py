@@ -48,7 +48,7 @@ def main(root: str, out: str) -> None:
             if k in d:
                 res[k][c.lower()] = d[k]
     res["_config"] = json.loads(os.environ.get("PMC_CONFIG", "null")) or \
-        {"command": "python3 bench.py --steps 3 --warmup 1 --no-cpu", "msgs_per_gpu": 1000000}
+        {"command": "python3 bench.py --full --steps 3 --warmup 1 --no-cpu", "msgs_per_gpu": 1000000}
     os.makedirs(os.path.dirname(out), exist_ok=True)
     with open(out, "w") as fh:
         json.dump(res, fh, indent=1)
