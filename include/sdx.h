@@ -317,8 +317,10 @@ enum sdx_line_status {
   SDX_LS_NOPARSER = 2,    /* no parser for the message type: ignored */
   SDX_LS_INVALID = 3,     /* the parser rejects the line (MU regex, MC header, MC hex, R/F): ignored */
   SDX_LS_NODATA = 4,      /* no D field: ignored */
-  SDX_LS_UNSUPPORTED = 5, /* outside the device contract (e.g. P# values outside the exact float() subset,
-                           * bytes >= 0x80 after decompression): the caller must not guess */
+  SDX_LS_UNSUPPORTED = 5, /* outside the device contract (e.g. bytes >= 0x80 after decompression, an R= of
+                           * more than 15 characters, an MC C= beyond int32): the caller must not guess.
+                           * sdx_parse_lines also reports MU/MS lines here whose P# values need more than
+                           * its one-operation float(); sdx_lines_exact resolves those */
   SDX_LS_RAISES = 6,      /* handed to the demodulator, which raises (caught by the parser): no results
                            * (MC: int(C) / int(L) of a hex-lettered value) */
   SDX_LS_GENERAL = 7      /* an MU/MS line the fixed-layout kernels do not take (a multi-digit pattern id,
@@ -383,6 +385,21 @@ typedef struct {
 
 int sdx_lines_general(const sdx_lines* lines, const sdx_lines_out* out, const int32_t* sel_dev, int32_t n_sel,
                       const sdx_lines_general_out* gen, void* hip_stream);
+
+/* The SDX_LS_UNSUPPORTED MU/MS lines of a finished sdx_parse_lines run, parsed again with the exact
+ * float(): for each selected line that is inside the contract apart from its P# values, writes what
+ * sdx_parse_lines + sdx_lines_general would have written (D into the line's slot region, doff/dlen,
+ * meta, the general-layout pattern table with exact values, cp slot, MS gates) and sets
+ * status_dev[i] = SDX_LS_GENERAL; any other line keeps SDX_LS_UNSUPPORTED and gets npat = 0 (and
+ * offsets[j] = len[j] = 0).  Same pointer alignment as sdx_parse_lines. */
+int sdx_lines_exact(const sdx_lines* lines, const sdx_lines_out* out, const int32_t* sel_dev, int32_t n_sel,
+                    const sdx_lines_general_out* gen, void* hip_stream);
+
+/* float(s) for n ASCII strings (strs->bytes_dev / offsets_dev as in sdx_parse_lines, same alignment and
+ * read-ahead rules): cls_dev[i] = 0 ValueError, 1 val_dev[i] is float(s) bit for bit,
+ * 2 the string holds a byte >= 0x80 (Python's Unicode digit/space handling is not modelled).
+ * val_dev[i] is 0.0 unless cls_dev[i] = 1. */
+int sdx_parse_floats(const sdx_lines* strs, double* val_dev, uint8_t* cls_dev, void* hip_stream);
 
 /* ---- publish-ready JSON ------------------------------------------------------
  * The MQTT publication of a DecodedMessage, MqttPublisher._message_to_json (signalduino/mqtt.py:

@@ -180,11 +180,16 @@ JD void emit(S& o, const sdx_json_in& in, const BankView& bv, const sdx_json_rec
     o.lit(",\n        \"clock\": ");
     if (in.kind == SDX_KIND_MU) {
       o.bytes(bv.str + j.s1_off, j.s1_len);  // json.dumps(float(clockabs))
-    } else {  // abs(P[CP]): an integral double (the front end parses <= 15 digits)
+    } else {  // abs(P[CP]): integral for firmware lines; float() syntax also gives halves ("377.5")
       const double c = fabs(in.pat_val_dev[10 * (int64_t)it.msg + in.cp_slot_dev[it.msg]]);
-      o.u64((uint64_t)c);
-      o.put('.');
-      o.put('0');
+      const double c2 = 2.0 * c;
+      if (c2 < 2e15 && c2 == floor(c2)) {
+        half_float(o, (int64_t)c2, false);
+      } else {
+        o.u64((uint64_t)c);
+        o.put('.');
+        o.put('0');
+      }
     }
   } else if (in.kind == SDX_KIND_MC) {  // {protocol_id, rssi: None, freq_afc: None}
     o.lit("\"protocol_id\": ");

@@ -14,13 +14,16 @@
 // The outputs of line i are message i of an sdx_pulse_batch / sdx_mc_batch in slot layout
 // (len_dev), so the demodulation kernels read them in place.  Anything whose exact Python meaning
 // this file does not model (bytes >= 0x80 after decompression, multi-digit pattern ids, non-integer
-// pattern values) is reported SDX_LS_UNSUPPORTED instead of being approximated.
+// pattern values) is reported SDX_LS_UNSUPPORTED instead of being approximated.  MU/MS lines that are
+// there only for P# values beyond parse_pyfloat's one-operation float() are resolved by a second stage,
+// sdx_lines_exact (k_lines_exact below, the correctly rounded conversion of sdx_strtod.h).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <string>
 
 #include "../../include/sdx.h"
+#include "sdx_strtod.h"
 
 namespace sdx {
 int set_error(int code, const std::string& msg);  // sdx_kernels.hip
@@ -1667,13 +1670,27 @@ LD bool id_string(const Str& P, int s, int e, uint8_t* dst) {
   return true;
 }
 
-__global__ __launch_bounds__(64) void k_lines_general(sdx_lines in, sdx_lines_out out, const int32_t* sel, int n_sel,
-                                                      sdx_lines_general_out g) {
+// EXACT = false: the SDX_LS_GENERAL rows (k_lines_general).  EXACT = true: the SDX_LS_UNSUPPORTED MU/MS
+// rows (k_lines_exact, sdx_lines_exact): the same rules with float() in full (sdxf::py_float behind
+// parse_pyfloat's class 2, digits in this lane's `scratch`), plus what k_parse_lines writes for a
+// line it accepts -- R/F (finish_fields), dlen, and for an uncompressed line the D characters and doff.
+template <bool EXACT>
+LD void lines_general_row(const sdx_lines& in, const sdx_lines_out& out, const int32_t* sel, int n_sel,
+                          const sdx_lines_general_out& g, uint8_t* scratch) {
   const int j = blockIdx.x * 64 + threadIdx.x;
   if (j >= n_sel) return;
   const int i = sel[j];
   const int64_t lo = in.offsets_dev[i];
   const int len = (int)(in.offsets_dev[i + 1] - lo);
+  if constexpr (EXACT) {  // rows that stay unsupported: an empty message
+    g.offsets_dev[j] = 0;
+    g.len_dev[j] = 0;
+    g.npat_dev[j] = 0;
+    g.cp_slot_dev[j] = -1;
+    g.ms_ok_dev[j] = 0;
+    const uint8_t kd = out.kind_dev[i];
+    if (out.status_dev[i] != SDX_LS_UNSUPPORTED || (kd != SDX_LINE_MU && kd != SDX_LINE_MS)) return;
+  }
   Str P;
   if (out.plen_dev[i] >= 0) {  // decompressed into the slot
     P = Str{out.slot_dev + 3 * lo, out.plen_dev[i]};
@@ -1684,11 +1701,17 @@ __global__ __launch_bounds__(64) void k_lines_general(sdx_lines in, sdx_lines_ou
     while (b > a && py_space(L[b - 1])) --b;
     P = Str{L + a + 1, b - a - 2};
   }
-  g.offsets_dev[j] = out.doff_dev[i];
-  g.len_dev[j] = out.dlen_dev[i];
+  if constexpr (EXACT) {
+    uint8_t any = 0;
+    for (int k = 0; k < P.n; ++k) any |= P.p[k];
+    if (any & 0x80) return;  // str methods on non-ASCII characters are not modelled
+  } else {
+    g.offsets_dev[j] = out.doff_dev[i];
+    g.len_dev[j] = out.dlen_dev[i];
+  }
   uint8_t* ids = g.pat_ids_dev + (int64_t)j * GEN_P * GEN_ID;
   double* vals = g.pat_val_dev + (int64_t)j * GEN_P;
-  Field fD{-1, -1}, fCP{-1, -1}, fSP{-1, -1}, fR{-1, -1};
+  Field fD{-1, -1}, fCP{-1, -1}, fSP{-1, -1}, fR{-1, -1}, fF{-1, -1};
   int pos = 0, s, e;
   while (next_part(P, pos, s, e)) {
     int k = s;
@@ -1698,6 +1721,10 @@ __global__ __launch_bounds__(64) void k_lines_general(sdx_lines in, sdx_lines_ou
     else if (keq(P, s, k, "CP")) fCP = f;
     else if (keq(P, s, k, "SP")) fSP = f;
     else if (keq(P, s, k, "R")) fR = f;
+    else if (EXACT && keq(P, s, k, "F")) fF = f;
+  }
+  if constexpr (EXACT) {  // no D (SDX_LS_NODATA, not seen here); meta_dev holds 15 bytes
+    if (fD.s < 0 || (fR.s >= 0 && fR.e - fR.s > 15) || (fF.s >= 0 && fF.e - fF.s > 15)) return;
   }
   const bool ms = out.kind_dev[i] == SDX_LINE_MS;
   bool ms_ok = ms && fD.s >= 0 && all_digits(P, fD.s, fD.e) && fCP.s >= 0 && all_digits(P, fCP.s, fCP.e) &&
@@ -1729,7 +1756,14 @@ __global__ __launch_bounds__(64) void k_lines_general(sdx_lines in, sdx_lines_ou
       }
     }
     double v;
-    const int rv = parse_pyfloat(P, vs, ve, &v);
+    int rv = parse_pyfloat(P, vs, ve, &v);
+    if constexpr (EXACT) {
+      if (rv == 2) {  // outside the one-operation subset: the digit-array conversion
+        uint64_t bits = 0;
+        rv = sdxf::py_float(P.p + vs, ve - vs, scratch, &bits);
+        v = __longlong_as_double((long long)bits);
+      }
+    }
     if (rv == 0) continue;  // float() raises ValueError: key skipped
     uint8_t id[GEN_ID];
     if (rv == 2 || !id_string(P, s + 1, ke, id)) {
@@ -1768,10 +1802,63 @@ __global__ __launch_bounds__(64) void k_lines_general(sdx_lines in, sdx_lines_ou
     out.status_dev[i] = SDX_LS_UNSUPPORTED;
     np = 0;
     ms_ok = false;
+    if constexpr (EXACT) cp = -1;
   }
   g.npat_dev[j] = (uint8_t)np;
   g.cp_slot_dev[j] = cp;
   g.ms_ok_dev[j] = ms_ok ? 1 : 0;
+  if constexpr (EXACT) {
+    if (bad) return;
+    LineRes r;
+    r.dS = fD.s;
+    r.dE = fD.e;
+    r.fR = fR;
+    r.fF = fF;
+    finish_fields(P, r, out, i);
+    int64_t doff = 3 * lo + fD.s;  // a decompressed payload lies in the slot, D inside it
+    if (out.plen_dev[i] < 0) {     // as k_parse_lines: word-aligned, inside the slot region (D < line length)
+      doff = (3 * lo + 3) & ~3ll;
+      for (int k = 0; k < fD.e - fD.s; ++k) out.slot_dev[doff + k] = P.p[fD.s + k];
+    }
+    out.doff_dev[i] = doff;
+    g.offsets_dev[j] = doff;
+    g.len_dev[j] = fD.e - fD.s;
+    out.status_dev[i] = SDX_LS_GENERAL;
+  }
+}
+
+__global__ __launch_bounds__(64) void k_lines_general(sdx_lines in, sdx_lines_out out, const int32_t* sel, int n_sel,
+                                                      sdx_lines_general_out g) {
+  lines_general_row<false>(in, out, sel, n_sel, g, nullptr);
+}
+
+// ---- the exact float(): LDS scratch of the digit-array conversion (csrc/sdx_strtod.h) ----------
+// One wave per workgroup, lane = string / line.  Each lane owns sdxf::kScratch = 804 contiguous
+// bytes (201 words, an odd count: lanes at the same digit index are 9 banks apart mod 64, all
+// different); 64 * 804 = 51456 bytes per workgroup, three workgroups per CU.  Only a lane whose value leaves
+// the one-operation fast path touches its column, in loops of its own length: no barrier anywhere.
+constexpr int FX_T = 64;
+static_assert(sdxf::kScratch % 4 == 0, "whole words per lane");
+
+__global__ __launch_bounds__(FX_T) void k_lines_exact(sdx_lines in, sdx_lines_out out, const int32_t* sel, int n_sel,
+                                                      sdx_lines_general_out g) {
+  __shared__ uint32_t sc[FX_T * (sdxf::kScratch / 4)];
+  lines_general_row<true>(in, out, sel, n_sel, g, reinterpret_cast<uint8_t*>(sc + threadIdx.x * (sdxf::kScratch / 4)));
+}
+
+__global__ __launch_bounds__(FX_T) void k_parse_floats(sdx_lines in, double* val, uint8_t* cls) {
+  __shared__ uint32_t sc[FX_T * (sdxf::kScratch / 4)];
+  const int i = blockIdx.x * FX_T + threadIdx.x;
+  if (i >= in.n) return;
+  const int64_t lo = in.offsets_dev[i];
+  const int64_t len = in.offsets_dev[i + 1] - lo;
+  uint64_t bits = 0;
+  int c = 0;  // longer than an int counts: not a float() any caller can ask for
+  if (len >= 0 && len <= 0x7FFFFFFF)
+    c = sdxf::py_float(in.bytes_dev + lo, (int)len, reinterpret_cast<uint8_t*>(sc + threadIdx.x * (sdxf::kScratch / 4)),
+                       &bits);
+  reinterpret_cast<uint64_t*>(val)[i] = c == 1 ? bits : 0;
+  cls[i] = (uint8_t)c;
 }
 
 }  // namespace sdxl
@@ -1839,5 +1926,38 @@ extern "C" int sdx_lines_general(const sdx_lines* lines, const sdx_lines_out* ou
                      sel_dev, n_sel, *gen);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return sdx::set_error(SDX_EHIP, std::string("sdx_lines_general: ") + hipGetErrorString(e));
+  return SDX_OK;
+}
+
+extern "C" int sdx_lines_exact(const sdx_lines* lines, const sdx_lines_out* out, const int32_t* sel_dev, int32_t n_sel,
+                               const sdx_lines_general_out* gen, void* hip_stream) {
+  if (!lines || !out || !gen || n_sel < 0) return sdx::set_error(SDX_EINVAL, "sdx_lines_exact: bad arguments");
+  if (n_sel == 0) return SDX_OK;
+  if (!sel_dev || !lines->bytes_dev || !lines->offsets_dev || !out->kind_dev || !out->status_dev || !out->slot_dev ||
+      !out->doff_dev || !out->dlen_dev || !out->meta_dev || !out->plen_dev || !gen->offsets_dev || !gen->len_dev ||
+      !gen->npat_dev || !gen->pat_ids_dev || !gen->pat_val_dev || !gen->cp_slot_dev || !gen->ms_ok_dev)
+    return sdx::set_error(SDX_EINVAL, "sdx_lines_exact: null buffer");
+  if (((uintptr_t)out->meta_dev & 15) != 0)
+    return sdx::set_error(SDX_EINVAL, "sdx_lines_exact: meta_dev must be 16-byte aligned");
+  if (((uintptr_t)lines->bytes_dev & 7) != 0 || ((uintptr_t)out->slot_dev & 7) != 0)
+    return sdx::set_error(SDX_EINVAL, "sdx_lines_exact: bytes_dev and slot_dev must be 8-byte aligned");
+  hipLaunchKernelGGL(sdxl::k_lines_exact, dim3((n_sel + sdxl::FX_T - 1) / sdxl::FX_T), dim3(sdxl::FX_T), 0,
+                     (hipStream_t)hip_stream, *lines, *out, sel_dev, n_sel, *gen);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return sdx::set_error(SDX_EHIP, std::string("sdx_lines_exact: ") + hipGetErrorString(e));
+  return SDX_OK;
+}
+
+extern "C" int sdx_parse_floats(const sdx_lines* strs, double* val_dev, uint8_t* cls_dev, void* hip_stream) {
+  if (!strs || strs->n < 0) return sdx::set_error(SDX_EINVAL, "sdx_parse_floats: bad arguments");
+  if (strs->n == 0) return SDX_OK;
+  if (!strs->bytes_dev || !strs->offsets_dev || !val_dev || !cls_dev)
+    return sdx::set_error(SDX_EINVAL, "sdx_parse_floats: null buffer");
+  if (((uintptr_t)strs->bytes_dev & 7) != 0 || ((uintptr_t)strs->offsets_dev & 7) != 0 || ((uintptr_t)val_dev & 7) != 0)
+    return sdx::set_error(SDX_EINVAL, "sdx_parse_floats: bytes_dev, offsets_dev and val_dev must be 8-byte aligned");
+  hipLaunchKernelGGL(sdxl::k_parse_floats, dim3((strs->n + sdxl::FX_T - 1) / sdxl::FX_T), dim3(sdxl::FX_T), 0,
+                     (hipStream_t)hip_stream, *strs, val_dev, cls_dev);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return sdx::set_error(SDX_EHIP, std::string("sdx_parse_floats: ") + hipGetErrorString(e));
   return SDX_OK;
 }

@@ -14,10 +14,12 @@ and only the result records come back.  The host side assembles the Python objec
 Observable behaviour per line is the reference's: ``parse_line`` returns the same
 ``DecodedMessage`` list (protocol_id, payload, metadata, raw.line / message_type / rssi /
 freq_afc), and lines the reference ignores give ``[]`` (a demodulator exception is caught and
-logged by the reference's parsers, so it also gives ``[]``).  Lines outside the device contract
-(multi-digit pattern ids, non-integer pattern values, non-ASCII characters after decompression,
-over-long messages, an MN R= of more than 15 digits) are never approximated: ``parse_line`` raises
-:class:`ContractError` and ``parse_lines`` returns the exception in that line's slot.
+logged by the reference's parsers, so it also gives ``[]``).  Pattern values are the reference's
+``float()`` in full: what sdx_parse_lines' one-operation conversion leaves open, sdx_lines_exact
+converts correctly rounded (csrc/sdx_strtod.h).  Lines outside the device contract (non-ASCII
+characters after decompression, pattern ids of more than 15 digits, more than 16 patterns, an R= /
+F= of more than 15 characters, an MC C= / L= beyond int32) are never approximated: ``parse_line``
+raises :class:`ContractError` and ``parse_lines`` returns the exception in that line's slot.
 There is no CPU fallback.
 """
 from __future__ import annotations
@@ -149,28 +151,48 @@ class LineBatch:
         return {"hex": self.slot, "offsets": self.doff, "len": self.dlen, "n": self.n}
 
     def general(self, status: np.ndarray, kind_np: np.ndarray, line_kind: int):
-        """The SDX_LS_GENERAL lines of one kind through sdx_lines_general + sdx_demod_pulses_general.
-        Returns (rows, desc, rec, heap, vals [rows, 16], cp_slot) or None when there are none; rows whose
-        general parse found them outside the contract are reported back in status (UNSUPPORTED)."""
+        """The SDX_LS_GENERAL lines of one kind through sdx_lines_general + sdx_demod_pulses_general,
+        together with the kind's SDX_LS_UNSUPPORTED lines that sdx_lines_exact resolves (P# values that
+        need the exact float(): they become SDX_LS_GENERAL rows of the same batch).
+        Returns (rows, desc, rec, heap, vals [rows, 16], cp_slot) or None when there are none; status is
+        updated in place: resolved rows turn GENERAL, rows the general parse found outside the contract
+        turn UNSUPPORTED (both kinds of UNSUPPORTED rows are left out of the returned batch)."""
         import ctypes
-        rows = np.nonzero((status == runtime.LS_GENERAL) & (kind_np == line_kind))[0]
+        of_kind = kind_np == line_kind
+        rows_g = np.nonzero((status == runtime.LS_GENERAL) & of_kind)[0]
+        rows_x = np.nonzero((status == runtime.LS_UNSUPPORTED) & of_kind)[0]
+        rows = np.concatenate([rows_g, rows_x])
         if not len(rows):
             return None
         t, d, eng = self.eng.torch, self.eng.dev, self.eng
-        m = len(rows)
+        m, mg = len(rows), len(rows_g)
         sel = t.from_numpy(rows.astype(np.int32)).to(d)
         g = {"offsets": t.empty(m, dtype=t.int64, device=d), "len": t.empty(m, dtype=t.int32, device=d),
              "npat": t.empty(m, dtype=t.uint8, device=d), "pat_ids": t.empty(m * 256, dtype=t.uint8, device=d),
              "pat_val": t.empty(m * 16, dtype=t.float64, device=d), "cp_slot": t.empty(m, dtype=t.int8, device=d),
              "ms_ok": t.empty(m, dtype=t.uint8, device=d)}
         p = runtime._ptr
-        go = runtime.SdxLinesGeneralOut(p(g["offsets"]), p(g["len"]), p(g["npat"]), p(g["pat_ids"]), p(g["pat_val"]),
-                                        p(g["cp_slot"]), p(g["ms_ok"]))
-        runtime._check(eng.lib, eng.lib.sdx_lines_general(ctypes.byref(self.c_lines), ctypes.byref(self.c_out),
-                                                          p(sel), m, ctypes.byref(go), eng.stream_ptr()))
-        lens = g["len"].cpu().numpy()
+        width = {"pat_ids": 256, "pat_val": 16}
+
+        def part(a, b):   # rows [a, b) of the batch as an sdx_lines_general_out
+            return runtime.SdxLinesGeneralOut(*(p(g[k][a * width.get(k, 1): b * width.get(k, 1)])
+                                                for k in ("offsets", "len", "npat", "pat_ids", "pat_val", "cp_slot", "ms_ok")))
+        if mg:
+            runtime._check(eng.lib, eng.lib.sdx_lines_general(ctypes.byref(self.c_lines), ctypes.byref(self.c_out),
+                                                              p(sel[:mg]), mg, ctypes.byref(part(0, mg)), eng.stream_ptr()))
+        if m > mg:
+            runtime._check(eng.lib, eng.lib.sdx_lines_exact(ctypes.byref(self.c_lines), ctypes.byref(self.c_out),
+                                                            p(sel[mg:]), m - mg, ctypes.byref(part(mg, m)), eng.stream_ptr()))
         st = self.status[sel.long()].cpu().numpy()
-        status[rows] = st                                   # lines found outside the contract
+        status[rows] = st                                   # resolved lines, lines found outside the contract
+        keep = np.nonzero(st == runtime.LS_GENERAL)[0]
+        if not len(keep):
+            return None
+        if len(keep) < m:
+            kd_ = t.from_numpy(keep).to(d)
+            g = {k: v.view(m, -1)[kd_].reshape(-1).contiguous() for k, v in g.items()}
+            rows, m = rows[keep], len(keep)
+        lens = g["len"].cpu().numpy()
         g.update(data=self.slot, n=m, total=int(lens.sum()), lens_host=lens)
         kd = runtime.KIND_MU if line_kind == runtime.LINE_MU else runtime.KIND_MS
         desc, rec, heap = eng.run_general(kd, g, work_stride=5 * (int(lens.max()) + 512))
@@ -518,9 +540,17 @@ class SignalParser:
                 texts[int(i)] = blob[int(offs[i]): int(offs[i]) + int(lens[i])].decode("ascii")
         status = lb.status[:n].cpu().numpy()
         kinds = lb.kind[:n].cpu().numpy()
-        grows = [int(i) for i in np.nonzero(status == runtime.LS_GENERAL)[0] if int(i) not in bad] + host_rows
+        # ... and the unsupported MU/MS lines with them: parse_lines resolves the ones whose P# values
+        # need the exact float() (sdx_lines_exact); the others come back as ContractError
+        exact = (status == runtime.LS_UNSUPPORTED) & ((kinds == runtime.LINE_MU) | (kinds == runtime.LINE_MS))
+        grows = [int(i) for i in np.nonzero((status == runtime.LS_GENERAL) | exact)[0] if int(i) not in bad] + host_rows
+        resolved = set()
         if grows:  # general-path lines (rare): their objects through parse_lines, the text as _message_to_json
             for i, g in zip(grows, self.parse_lines([lines[i] for i in grows])):
+                if exact[i]:
+                    if isinstance(g, ContractError):
+                        continue   # still unsupported: reported below, under its index in this batch
+                    resolved.add(i)
                 if isinstance(g, BaseException):
                     texts[i] = g
                 elif g:
@@ -529,7 +559,7 @@ class SignalParser:
         for i in range(n):
             if i in bad:
                 texts[i] = bad[i]
-            elif int(status[i]) == runtime.LS_UNSUPPORTED:
+            elif int(status[i]) == runtime.LS_UNSUPPORTED and i not in resolved:
                 texts[i] = ContractError(f"line {i} is outside the device contract of the front end "
                                          f"(kind {_KIND_NAME.get(int(kinds[i]), '?')})")
         return texts

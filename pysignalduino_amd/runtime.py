@@ -11,7 +11,7 @@ import ctypes
 import os
 import struct
 from ctypes import POINTER, Structure, c_char_p, c_int, c_int32, c_size_t, c_uint32, c_void_p
-from typing import Dict, Optional, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -45,7 +45,7 @@ EXPORTED = ["sdx_abi_version", "sdx_last_error", "sdx_source_hash", "sdx_layout_
             "sdx_exchange_work_bytes", "sdx_exchange_send_bytes", "sdx_exchange_count", "sdx_exchange_pack", "sdx_exchange_pack_into", "sdx_exchange_unpack_work_bytes",
             "sdx_exchange_unpack", "sdx_pulses_work_bytes", "sdx_group_work_bytes", "sdx_group_pulses",
             "sdx_general_work_bytes", "sdx_demod_pulses_general", "sdx_mc_general_work_bytes", "sdx_demod_mc_general",
-            "sdx_lines_general", "sdx_copy_async", "sdx_copy_async_kind", "sdx_copy_async_narrow",
+            "sdx_lines_general", "sdx_lines_exact", "sdx_parse_floats", "sdx_copy_async", "sdx_copy_async_kind", "sdx_copy_async_narrow",
             "sdx_fill_async", "sdx_demod_step", "sdx_group_step"]
 GROUP_MIN = int(os.environ.get("SDX_GROUP_MIN", "4096"))   # SDX_GROUP_MIN (the env: A/B of the grouping)
 
@@ -210,6 +210,11 @@ def load_library(path: Optional[str] = None):
     lib.sdx_lines_general.argtypes = [POINTER(SdxLines), POINTER(SdxLinesOut), c_void_p, c_int32,
                                       POINTER(SdxLinesGeneralOut), c_void_p]
     lib.sdx_lines_general.restype = c_int
+    lib.sdx_lines_exact.argtypes = [POINTER(SdxLines), POINTER(SdxLinesOut), c_void_p, c_int32,
+                                    POINTER(SdxLinesGeneralOut), c_void_p]
+    lib.sdx_lines_exact.restype = c_int
+    lib.sdx_parse_floats.argtypes = [POINTER(SdxLines), c_void_p, c_void_p, c_void_p]
+    lib.sdx_parse_floats.restype = c_int
     lib.sdx_demod_mc.argtypes = [c_void_p, POINTER(SdxMcBatch), POINTER(SdxOut), c_void_p]
     lib.sdx_group_step.restype = c_int
     lib.sdx_group_step.argtypes = [c_void_p, POINTER(SdxGroupJob), POINTER(SdxGroupJob), c_void_p]
@@ -881,3 +886,20 @@ class UnitRunner:
         rec = out["rec"].cpu().numpy().view(RES_DT).copy()
         heap = out["heap"].cpu().numpy()
         return desc, rec, heap
+
+    def parse_floats(self, strs: Sequence[bytes]):
+        """sdx_parse_floats over the byte strings: (cls uint8[n], bits uint64[n]) as host numpy arrays."""
+        t, d = self.torch, self.dev
+        n = len(strs)
+        if n == 0:
+            return np.zeros(0, np.uint8), np.zeros(0, np.uint64)
+        off = np.zeros(n + 1, np.int64)
+        np.cumsum(np.fromiter((len(b) for b in strs), np.int64, n), out=off[1:])
+        data = t.from_numpy(np.frombuffer(b"".join(strs) + b"\0" * 16, np.uint8).copy()).to(d)
+        offs = t.from_numpy(off).to(d)
+        val = t.empty(n, dtype=t.float64, device=d)
+        cls = t.empty(n, dtype=t.uint8, device=d)
+        b = SdxLines(_ptr(data), _ptr(offs), n)
+        _check(self.lib, self.lib.sdx_parse_floats(ctypes.byref(b), _ptr(val), _ptr(cls),
+                                                   c_void_p(t.cuda.current_stream(d).cuda_stream)))
+        return cls.cpu().numpy(), val.cpu().numpy().view(np.uint64)

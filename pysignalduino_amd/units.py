@@ -387,6 +387,28 @@ class UnitsMixin:
     def mc2dmc(self, bit_data):  # helpers.py:6
         return self.mc2dmc_batch([bit_data])[0]
 
+    def float_batch(self, values: Sequence[Any]) -> List[Any]:
+        """``float(v)`` of every str / bytes value in one launch (sdx_parse_floats: correctly rounded,
+        csrc/sdx_strtod.h) -- the conversion the reference applies to every P# value
+        (message_unsynced.py:28-35).  A ValueError instance stands in the slot where float() raises."""
+        ins = []
+        for v in values:
+            if isinstance(v, str):
+                b = _ascii(v, "float")
+            elif isinstance(v, (bytes, bytearray)):
+                b = bytes(v)
+                if any(c >= 0x80 for c in b):
+                    raise ContractError("float: non-ASCII text is not modelled on the device")
+            else:
+                raise ContractError("float: only str / bytes input is modelled on the device")
+            ins.append(b)
+        cls, bits = runtime.UnitRunner.get(self.device).parse_floats(ins)
+        if (cls == 2).any():
+            raise ContractError("float: non-ASCII text is not modelled on the device")
+        vals = bits.view(np.float64).tolist()   # nan keeps its bits through tolist()
+        return [vals[i] if c == 1 else ValueError(f"could not convert string to float: {values[i]!r}")
+                for i, c in enumerate(cls.tolist())]
+
     @staticmethod
     def dec_2_bin_ppari(num):  # helpers.py:66-88 (8-bit format + parity: integer formatting, host)
         if num is None:
