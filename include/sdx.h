@@ -400,6 +400,11 @@ int sdx_lines_exact(const sdx_lines* lines, const sdx_lines_out* out, const int3
  * 2 the string holds a byte >= 0x80 (Python's Unicode digit/space handling is not modelled).
  * val_dev[i] is 0.0 unless cls_dev[i] = 1. */
 int sdx_parse_floats(const sdx_lines* strs, double* val_dev, uint8_t* cls_dev, void* hip_stream);
+/* repr(x) (json_form = 0) or json.dumps(x) (1) of n doubles: text_dev[32*i .. ] holds the ASCII text,
+ * byte 32*i + 31 its length (<= 24); the bytes between are zero.  The shortest digits that convert
+ * back to x, in Python's formatting (csrc/sdx_dtoa.h); nan and the infinities as "nan" / "inf" / "-inf",
+ * with json_form "NaN" / "Infinity" / "-Infinity".  val_dev and text_dev must be 8-byte aligned. */
+int sdx_format_floats(const double* val_dev, int32_t n, int32_t json_form, uint8_t* text_dev, void* hip_stream);
 
 /* ---- publish-ready JSON ------------------------------------------------------
  * The MQTT publication of a DecodedMessage, MqttPublisher._message_to_json (signalduino/mqtt.py:
@@ -407,7 +412,8 @@ int sdx_parse_floats(const sdx_lines* strs, double* val_dev, uint8_t* cls_dev, v
  *   {"protocol_id": ..., "payload": ..., "metadata": {...}} with Python's separators, indentation,
  *   float repr and ensure_ascii escapes,
  * built on the device from one demodulation launch's outputs and the front end's per-line fields
- * (meta.rssi = the raw R string for MU/MS, meta.clock = float(clockabs) / abs(P[CP]); MC: protocol_id,
+ * (meta.rssi = the raw R string for MU/MS, meta.clock = float(clockabs) / abs(P[CP]), any double, as
+ * float.__repr__ prints it (csrc/sdx_dtoa.h); MC: protocol_id,
  * rssi/freq_afc null; MN: calc_rssi(R), round(26000000/16384*A/1000, 0), modulation, rfmode).
  * first_only = 1 gives the one message per line the controller publishes (decoded[0],
  * signalduino/controller.py:254-257); 0 gives one JSON text per result record; 2 (ABI 11) is 1 but

@@ -23,6 +23,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 DEPS = [*SRCS, os.path.join(HERE, "csrc", "sdx_device.h"), os.path.join(HERE, "csrc", "sdx_lane.h"),
         os.path.join(HERE, "csrc", "sdx_mc.h"),
         os.path.join(HERE, "csrc", "sdx_strtod.h"),      # exact float(), host + device (sdx_lines.hip)
+        os.path.join(HERE, "csrc", "sdx_dtoa.h"),        # repr(float), host + device (sdx_json.hip)
+        os.path.join(HERE, "csrc", "sdx_dtoa_pow10.h"),  # its powers of ten (tools/gen_dtoa_pow10.py)
         os.path.join(os.path.dirname(HERE), "include", "sdx.h"),
         os.path.join(os.path.dirname(HERE), "include", "sdx_bank.h")]
 

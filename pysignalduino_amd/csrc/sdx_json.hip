@@ -8,14 +8,16 @@
 // demodulators (message_unsynced.py:282-290, message_synced.py:233-241, sd_protocols.py:102-109 +
 // manchester.py:136-140, parser/mn.py:181-191), so the texts are built here from fragments:
 // protocol strings pre-rendered by Python's json on the host (bank.py, sdx_json_rec), the payload
-// bytes of the demodulation launch, and the per-line fields of the front end.  The only floats the
-// device prints are integral or half-integral values below 1e15 (abs(P[CP]), calc_rssi,
-// round(..., 0)), whose repr is "<integer>.0" / "<integer>.5".
+// bytes of the demodulation launch, and the per-line fields of the front end.  The floats the
+// device prints are integral or half-integral values below 1e15 (abs(P[CP]) of firmware lines,
+// calc_rssi, round(..., 0)), whose repr is "<integer>.0" / "<integer>.5", and for any other MS
+// clock float.__repr__ in full (sdxf::py_repr_to, csrc/sdx_dtoa.h).
 //
 // Lane = published item (a line's first result, or one result record).  Pass 1 sizes the text
 // (Count sink), one wave prefix sum + one atomic reserve the bytes, pass 2 writes them (J8 sink,
 // aligned 8-byte stores into the lane's own range).
 #include "sdx_device.h"
+#include "sdx_dtoa.h"
 
 #include <string>
 
@@ -185,10 +187,8 @@ JD void emit(S& o, const sdx_json_in& in, const BankView& bv, const sdx_json_rec
       const double c2 = 2.0 * c;
       if (c2 < 2e15 && c2 == floor(c2)) {
         half_float(o, (int64_t)c2, false);
-      } else {
-        o.u64((uint64_t)c);
-        o.put('.');
-        o.put('0');
+      } else {  // any other double: json.dumps(c) (csrc/sdx_dtoa.h)
+        sdxf::py_repr_to(c, true, o);
       }
     }
   } else if (in.kind == SDX_KIND_MC) {  // {protocol_id, rssi: None, freq_afc: None}
@@ -280,7 +280,52 @@ __global__ __launch_bounds__(JT) void k_json(const void* __restrict__ bank, sdx_
   w.finish();
 }
 
+// ---- sdx_format_floats: lane = value, 32 bytes of output per lane as four aligned 8-byte stores
+constexpr int FT = 256;
+
+struct W8 {  // the text's bytes gathered into 8-byte words, stored as each fills
+  uint64_t* w;
+  uint64_t acc;
+  int fill;
+  JD void put(uint8_t c) {
+    acc |= (uint64_t)c << (8 * fill);
+    if (++fill == 8) {
+      *w++ = acc;
+      acc = 0;
+      fill = 0;
+    }
+  }
+};
+
+__global__ __launch_bounds__(FT) void k_format_floats(const double* __restrict__ val, int n, int json_form,
+                                                      uint8_t* __restrict__ text) {
+  const int g = blockIdx.x * FT + threadIdx.x;
+  if (g >= n) return;
+  uint64_t* row = reinterpret_cast<uint64_t*>(text + 32 * (int64_t)g);
+  W8 o{row, 0, 0};
+  const int len = sdxf::py_repr_to(val[g], json_form != 0, o);  // <= 24: never reaches word 3
+  for (uint64_t* p = o.w; p < row + 3; ++p) {  // the partial word, then zeros
+    *p = o.acc;
+    o.acc = 0;
+  }
+  row[3] = (uint64_t)len << 56;
+}
+
 }  // namespace sdxj
+
+extern "C" int sdx_format_floats(const double* val_dev, int32_t n, int32_t json_form, uint8_t* text_dev,
+                                 void* hip_stream) {
+  if (n < 0) return sdx::set_error(SDX_EINVAL, "sdx_format_floats: n < 0");
+  if (n == 0) return SDX_OK;
+  if (!val_dev || !text_dev) return sdx::set_error(SDX_EINVAL, "sdx_format_floats: null buffer");
+  if (((uintptr_t)val_dev | (uintptr_t)text_dev) & 7)
+    return sdx::set_error(SDX_EINVAL, "sdx_format_floats: val_dev and text_dev must be 8-byte aligned");
+  hipLaunchKernelGGL(sdxj::k_format_floats, dim3((n + sdxj::FT - 1) / sdxj::FT), dim3(sdxj::FT), 0,
+                     (hipStream_t)hip_stream, val_dev, (int)n, (int)json_form, text_dev);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return sdx::set_error(SDX_EHIP, std::string("sdx_format_floats: ") + hipGetErrorString(e));
+  return SDX_OK;
+}
 
 extern "C" int sdx_serialize_json(const sdx_bank* bank, const sdx_json_in* in, const sdx_json_out* out,
                                   void* hip_stream) {

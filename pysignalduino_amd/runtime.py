@@ -45,7 +45,7 @@ EXPORTED = ["sdx_abi_version", "sdx_last_error", "sdx_source_hash", "sdx_layout_
             "sdx_exchange_work_bytes", "sdx_exchange_send_bytes", "sdx_exchange_count", "sdx_exchange_pack", "sdx_exchange_pack_into", "sdx_exchange_unpack_work_bytes",
             "sdx_exchange_unpack", "sdx_pulses_work_bytes", "sdx_group_work_bytes", "sdx_group_pulses",
             "sdx_general_work_bytes", "sdx_demod_pulses_general", "sdx_mc_general_work_bytes", "sdx_demod_mc_general",
-            "sdx_lines_general", "sdx_lines_exact", "sdx_parse_floats", "sdx_copy_async", "sdx_copy_async_kind", "sdx_copy_async_narrow",
+            "sdx_lines_general", "sdx_lines_exact", "sdx_parse_floats", "sdx_format_floats", "sdx_copy_async", "sdx_copy_async_kind", "sdx_copy_async_narrow",
             "sdx_fill_async", "sdx_demod_step", "sdx_group_step"]
 GROUP_MIN = int(os.environ.get("SDX_GROUP_MIN", "4096"))   # SDX_GROUP_MIN (the env: A/B of the grouping)
 
@@ -215,6 +215,8 @@ def load_library(path: Optional[str] = None):
     lib.sdx_lines_exact.restype = c_int
     lib.sdx_parse_floats.argtypes = [POINTER(SdxLines), c_void_p, c_void_p, c_void_p]
     lib.sdx_parse_floats.restype = c_int
+    lib.sdx_format_floats.argtypes = [c_void_p, c_int32, c_int32, c_void_p, c_void_p]
+    lib.sdx_format_floats.restype = c_int
     lib.sdx_demod_mc.argtypes = [c_void_p, POINTER(SdxMcBatch), POINTER(SdxOut), c_void_p]
     lib.sdx_group_step.restype = c_int
     lib.sdx_group_step.argtypes = [c_void_p, POINTER(SdxGroupJob), POINTER(SdxGroupJob), c_void_p]
@@ -812,6 +814,10 @@ class Engine:
         heap = out["heap"][:nheap].cpu().numpy().copy()
         return desc, rec, heap
 
+    def format_floats(self, values, json_form: bool = False) -> "list[bytes]":
+        """sdx_format_floats on this engine's device: repr(x) / json.dumps(x) of every double, as bytes."""
+        return UnitRunner.get(self.device).format_floats(values, json_form)
+
 
 # ---- unit-level entry (sdx_units) ----------------------------------------------------------------
 UNIT_POSTDEMO, UNIT_HEX2BIN, UNIT_BIN2HEX, UNIT_MC2DMC, UNIT_PEXISTS, UNIT_MC_METHOD = 1, 2, 3, 4, 5, 6
@@ -903,3 +909,24 @@ class UnitRunner:
         _check(self.lib, self.lib.sdx_parse_floats(ctypes.byref(b), _ptr(val), _ptr(cls),
                                                    c_void_p(t.cuda.current_stream(d).cuda_stream)))
         return cls.cpu().numpy(), val.cpu().numpy().view(np.uint64)
+
+    def format_floats(self, values, json_form: bool = False) -> "list[bytes]":
+        """sdx_format_floats over the doubles (a float64 array, or a uint64 array of bit patterns):
+        repr(x), or json.dumps(x) with ``json_form``, of each as ASCII bytes."""
+        t, d = self.torch, self.dev
+        a = np.asarray(values)
+        a = a.view(np.float64) if a.dtype == np.uint64 else a.astype(np.float64)
+        a = np.ascontiguousarray(a).reshape(-1)
+        n = len(a)
+        if n == 0:
+            return []
+        val = t.from_numpy(a.view(np.int64).copy()).to(d)      # bit patterns: a nan keeps its payload
+        text = t.empty(32 * n, dtype=t.uint8, device=d)
+        _check(self.lib, self.lib.sdx_format_floats(_ptr(val), n, 1 if json_form else 0, _ptr(text),
+                                                    c_void_p(t.cuda.current_stream(d).cuda_stream)))
+        rows = text.cpu().numpy().reshape(n, 32)
+        lens = rows[:, 31].tolist()
+        if max(lens) > 24:
+            raise RuntimeError("sdx_format_floats: a text longer than 24 bytes")
+        flat = rows.tobytes()
+        return [flat[32 * i: 32 * i + k] for i, k in enumerate(lens)]

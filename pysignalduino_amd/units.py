@@ -409,6 +409,16 @@ class UnitsMixin:
         return [vals[i] if c == 1 else ValueError(f"could not convert string to float: {values[i]!r}")
                 for i, c in enumerate(cls.tolist())]
 
+    def repr_batch(self, values: Sequence[Any], json_form: bool = False) -> List[str]:
+        """``repr(v)`` of every float in one launch, or ``json.dumps(v)`` with ``json_form``
+        (sdx_format_floats, csrc/sdx_dtoa.h: the shortest digits that ``float()`` reads back, in
+        Python's formatting) -- the inverse of :meth:`float_batch`."""
+        for v in values:
+            if not isinstance(v, float):           # np.float64 is a float; int / str / None are not
+                raise ContractError("repr: only float input is modelled on the device")
+        a = np.fromiter(values, np.float64, len(values))
+        return [b.decode("ascii") for b in runtime.UnitRunner.get(self.device).format_floats(a, json_form)]
+
     @staticmethod
     def dec_2_bin_ppari(num):  # helpers.py:66-88 (8-bit format + parity: integer formatting, host)
         if num is None:
