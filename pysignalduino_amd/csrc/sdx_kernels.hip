@@ -179,13 +179,21 @@ struct TileLds {
   typename std::conditional<LM != 0, NoScratch, WaveScratch4>::type wa;
   // short MS tiles (NW <= 4, not the MU lane variant) stage few results; overflow re-runs on the
   // long variant
-  static constexpr int PREC = LM == 1 ? 512 : (NW <= 4 ? POOL_REC_MS : POOL_REC);
-  static constexpr int PHEAP = LM == 1 ? 10240 : (NW <= 4 ? POOL_HEAP_MS : POOL_HEAP);  // MU bench tiles: <= 8.1 KB
+  // the 128-message MS tile pools what two 64-message tiles had: the same room per message
+  static constexpr int PREC = LM == 1 ? 512 : (NW <= 4 ? POOL_REC_MS * (TM > 64 ? 2 : 1) : POOL_REC);
+  static constexpr int PHEAP =
+      LM == 1 ? 10240 : (NW <= 4 ? POOL_HEAP_MS * (TM > 64 ? 2 : 1) : POOL_HEAP);  // MU bench tiles: <= 8.1 KB
+  // MS survivors per tile (128 messages: what fits beside the larger bitmaps and pools)
+  static constexpr int SCAP = TM > 64 ? MS_SURV_CAP + MS_SURV_CAP / 4 : MS_SURV_CAP;
+  // protocol counters: the lane-decode MS tile of 128 messages runs as two halves of 64 (waves 0-3,
+  // waves 4-7), each half's waves sharing that half's protocols
+  static constexpr int NHALF = (LM == 2 && TM > 64) ? 2 : 1;
+  static_assert(TM <= 64 * NHALF, "one lane per message of a half");
   StageRec rec[PREC];
   alignas(16) uint8_t heap[PHEAP];
   unsigned long long pool_ctr;  // low 32: staged records, high 32: staged heap bytes (one LDS atomic)
   uint32_t spill_base, sp_rec, sp_heap;  // the tile's spill region (SPILL_NONE: none yet) and its fill
-  int ovf, next_p;
+  int ovf, next_p[NHALF];
   int mm_states, nmatch;
   MuMatch mlist[LM == 1 ? MATCH_CAP : 1];
   alignas(16) sdx_mu_desc desc[LM == 1 ? SDX_MUDESC_LDS : 1];
@@ -196,7 +204,7 @@ struct TileLds {
     uint8_t mmtab[LM == 1 ? SDX_MMTAB_LDS : 16];
   } u;
   // MS survivors of the whole tile, decoded after the protocol loop with lane = survivor
-  MsItem slist[LM == 2 ? MS_SURV_CAP : 1];
+  MsItem slist[LM == 2 ? SCAP : 1];
   int nsurv;
   MsDesc msdesc[LM == 2 ? MS_DESC_LDS : 1];
 #ifdef SDX_PROF
@@ -1397,18 +1405,30 @@ SDX_DEV void flush_tile(TileLds<NW, TM, LM>& L, const int* msg_of, int nvalid, c
     }
   __syncthreads();
   const uint32_t nh_l16 = ((uint32_t)nh_l + 15u) & ~15u;
-  static_assert(TM <= 64, "one wave scans the tile's messages");
-  if (tid < 64) {  // wave 0, lane = message: the record base of every message (exclusive scan)
+  constexpr int MPL = (TM + 63) / 64;  // messages per lane of the scanning wave (consecutive)
+  if (tid < 64) {  // wave 0, lane = MPL messages: the record base of every message (exclusive scan)
     const int lane = tid;
-    const bool live = !ovf && lane < nvalid && L.raise_key[lane] == 0xFFFFFFFFu;
-    const uint32_t c = live ? cntm[lane] : 0u;
+    uint32_t cm[MPL], c = 0;
+#pragma unroll
+    for (int k = 0; k < MPL; ++k) {
+      const int m = lane * MPL + k;
+      const bool live = !ovf && m < TM && m < nvalid && L.raise_key[m] == 0xFFFFFFFFu;
+      cm[k] = live ? cntm[m] : 0u;
+      c += cm[k];
+    }
     uint32_t x = c;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
       const uint32_t y = __shfl_up(x, o);
       if (lane >= o) x += y;
     }
-    if (lane < nvalid) L.mbase[lane] = x - c;
+    uint32_t mb = x - c;
+#pragma unroll
+    for (int k = 0; k < MPL; ++k) {
+      const int m = lane * MPL + k;
+      if (m < TM && m < nvalid) L.mbase[m] = mb;
+      mb += cm[k];
+    }
     const uint32_t nrec = __shfl(x, 63);
     // 16-B pieces: full-width copies
     const uint32_t nheap = ovf ? 0u : nh_l16 + (((uint32_t)nh_s + 15u) & ~15u);
@@ -1566,7 +1586,8 @@ SDX_DEV void pulses_tile(const void* __restrict__ bank, const sdx_pulse_batch& b
     L.cnt[tid] = 0;
   }
   if (tid == 0) {
-    L.next_p = 0;
+#pragma unroll
+    for (int h = 0; h < T::NHALF; ++h) L.next_p[h] = 0;
     L.nmatch = 0;
     L.pool_ctr = 0;
     L.spill_base = SPILL_NONE;
@@ -1832,8 +1853,10 @@ SDX_DEV void pulses_tile(const void* __restrict__ bank, const sdx_pulse_batch& b
   }
   __syncthreads();
   PROF_ADD(0, t_stage);
-  // ---- per-lane message state (lane = message of the tile)
-  const int mi = lane;
+  // ---- per-lane message state (lane = message of the tile; of the wave's half in a 128-message
+  // tile: waves 0-3 hold messages 0..63, waves 4-7 messages 64..127)
+  const int half = T::NHALF > 1 ? wave / (NWAVE / T::NHALF) : 0;
+  const int mi = lane + 64 * half;
   const bool mvalid = mi < nvalid;
   int npat = 0, n = 0;
   uint64_t ids = 0;
@@ -1965,7 +1988,7 @@ SDX_DEV void pulses_tile(const void* __restrict__ bank, const sdx_pulse_batch& b
   while (true) {
     if (cur == cend) {
       int g = 0;
-      if (lane == 0) g = atomicAdd(&L.next_p, 1);
+      if (lane == 0) g = atomicAdd(&L.next_p[half], 1);
       g = __builtin_amdgcn_readfirstlane(g);
 #ifdef SDX_PROF
       if (g_cur >= 0 && g_cur < 128 && lane == 0) {
@@ -1975,7 +1998,7 @@ SDX_DEV void pulses_tile(const void* __restrict__ bank, const sdx_pulse_batch& b
       g_cur = g;
       g_t0 = __builtin_amdgcn_s_memtime();
 #endif
-      if (g >= ngrab) break;
+      if (g >= ngrab || (T::NHALF > 1 && 64 * half >= nvalid)) break;  // (a half without messages)
       if (KIND == SDX_KIND_MU) {
         cur = cld(&gstart[g]);
         cend = cld(&gstart[g + 1]);
@@ -2162,7 +2185,7 @@ SDX_DEV void pulses_tile(const void* __restrict__ bank, const sdx_pulse_batch& b
           if (lane == 0) base = atomicAdd(&L.nsurv, popc64(pass));
           base = __builtin_amdgcn_readfirstlane(base);
           const int slot = base + lanes_below(pass);
-          if (alive && slot < MS_SURV_CAP) {
+          if (alive && slot < T::SCAP) {
             MsItem it;
             it.k0_lo = (uint32_t)kt0;
             it.k0_hi = (uint32_t)(kt0 >> 32);
@@ -2175,7 +2198,7 @@ SDX_DEV void pulses_tile(const void* __restrict__ bank, const sdx_pulse_batch& b
             it.fmask = (uint8_t)fmask;
             L.slist[slot] = it;
           }
-          if (base + popc64(pass) > MS_SURV_CAP && lane == 0) L.ovf = 1;  // tile re-run (long variant)
+          if (base + popc64(pass) > T::SCAP && lane == 0) L.ovf = 1;  // tile re-run (long variant)
         }
       } else {
         uint64_t surv = ballot(alive);
@@ -2202,7 +2225,7 @@ SDX_DEV void pulses_tile(const void* __restrict__ bank, const sdx_pulse_batch& b
   PROF_ADD(14, t_bar);
   if constexpr (LANE_MS) {  // decode every survivor of the tile: lane = (message, protocol)
     PROF_T(t_dec);
-    const int ns = L.nsurv < MS_SURV_CAP ? L.nsurv : MS_SURV_CAP;
+    const int ns = L.nsurv < T::SCAP ? L.nsurv : T::SCAP;
     if (!L.ovf) {
       // survivors packed into the first waves (dealing them round-robin over all 8 measured
       // 0.73 vs 0.645 ms: more waves on the same divergent decode path)
@@ -2987,35 +3010,60 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LONG ? 1 : 
 // workgroup exists only to find that the tile is another launch's.  MR = 1: the header fields (and the
 // length deciding the class) from the message records the grouping wrote (one 128-byte line per
 // message instead of a sector of each SoA field)
+// tm = 128 (large batches): workgroup w owns messages [128 w, 128 w + 128) of the order.  When none has
+// more than 128 pulses they run as one 128-message NW = 2 tile, so the per-tile phases that keep
+// one or two of the eight waves busy (survivor decode, flush scan) come half as often per message;
+// otherwise as the 64-message NW = 4 tiles 2 w and 2 w + 1, one after the other in the same LDS.
+// tm = 64: workgroup w is tile w, as before.  tm is block-uniform (a kernel argument)
+union MsLds {
+  PulsesLds<SDX_KIND_MS, 2, 64> n2;
+  PulsesLds<SDX_KIND_MS, 4, 64> n4;
+  PulsesLds<SDX_KIND_MS, 2, 128> w2;
+};
+constexpr int MS_TM_MAX = 128;  // msg_of[] of the kernels that run MS tiles
 template <int MR>
 SDX_DEV void ms_tile_by_class(const void* __restrict__ bank, const sdx_pulse_batch& b, const sdx_out& out, const int w,
-                              PulsesLds<SDX_KIND_MS, 2, 64>& L2, PulsesLds<SDX_KIND_MS, 4, 64>& L4, int* msg_of) {
+                              const int tm, MsLds& L, int* msg_of) {
   const int ntot = b.sel_dev ? b.n_sel : b.n;
-  const int m = w * 64 + (int)threadIdx.x;
+  const int m = w * tm + (int)threadIdx.x;
   int len = 0;
-  if (threadIdx.x < 64 && m < ntot) {
+  if ((int)threadIdx.x < tm && m < ntot) {
     const int msg = b.sel_dev ? b.sel_dev[m] : m;
     if (MR)
       len = b.mrec_dev[msg].len;
     else
       len = b.len_dev ? b.len_dev[msg] : (int)(b.offsets_dev[msg + 1] - b.offsets_dev[msg]);
   }
-  if (__syncthreads_or(len > 128) == 0)
-    pulses_tile<SDX_KIND_MS, 2, 64, MR, 0>(bank, b, out, w, L2, msg_of);
-  else
-    pulses_tile<SDX_KIND_MS, 4, 64, MR, 0>(bank, b, out, w, L4, msg_of);
+  const bool wide = __syncthreads_or(len > 128) != 0;
+  int t0 = w, nt = 1;
+  if (tm > 64) {
+    if (!wide) {
+      pulses_tile<SDX_KIND_MS, 2, 128, MR, 0>(bank, b, out, w, L.w2, msg_of);
+      return;
+    }
+    t0 = 2 * w;
+    nt = (t0 + 1) * 64 < ntot ? 2 : 1;
+  }
+  if (!wide) {
+    pulses_tile<SDX_KIND_MS, 2, 64, MR, 0>(bank, b, out, w, L.n2, msg_of);
+  } else {
+    // (two calls, not a loop over the tile: values hoisted out of such a loop stayed live across the
+    // whole tile and spilled ~130 VGPRs)
+    pulses_tile<SDX_KIND_MS, 4, 64, MR, 0>(bank, b, out, t0, L.n4, msg_of);
+    if (nt > 1) {
+      __syncthreads();  // the first tile's flush still reads the LDS the next one initialises
+      pulses_tile<SDX_KIND_MS, 4, 64, MR, 0>(bank, b, out, t0 + 1, L.n4, msg_of);
+    }
+  }
 }
 
 // sdx_demod_pulses(MS): every tile on its length class's instantiation
 template <int MR>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k_ms_classes(
-    const void* __restrict__ bank, sdx_pulse_batch b, sdx_out out) {
-  __shared__ union {
-    PulsesLds<SDX_KIND_MS, 2, 64> n2;
-    PulsesLds<SDX_KIND_MS, 4, 64> n4;
-  } U;
-  __shared__ int msg_of[64];
-  ms_tile_by_class<MR>(bank, b, out, (int)blockIdx.x, U.n2, U.n4, msg_of);
+    const void* __restrict__ bank, sdx_pulse_batch b, sdx_out out, int tm) {
+  __shared__ MsLds U;
+  __shared__ int msg_of[MS_TM_MAX];
+  ms_tile_by_class<MR>(bank, b, out, (int)blockIdx.x, tm, U, msg_of);
 }
 
 struct StepArgs {
@@ -3023,21 +3071,22 @@ struct StepArgs {
   sdx_mc_batch mc;
   sdx_out mu_out, ms_out, mc_out;
   int t_mu, t_ms, b_mc;  // workgroups of each range (b_mc: pairs of 256-frame blocks)
+  int ms_tm;             // messages per MS workgroup: 64 or 128 (ms_tile_by_class)
 };
 union StepLds {
   PulsesLds<SDX_KIND_MU, 4, 64> mu;
-  PulsesLds<SDX_KIND_MS, 2, 64> ms2;
-  PulsesLds<SDX_KIND_MS, 4, 64> ms4;
+  MsLds ms;
   McLdsC<MC_SHORTW> mc[2];
 };
 static_assert(sizeof(StepLds) <= 81920, "two k_step workgroups per CU (160 KB of LDS)");
+static_assert(sizeof(StepLds) + MS_TM_MAX * sizeof(int) <= 81920, "... with the kernel's msg_of[]");
 
 template <int MRU, int MRS>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k_step(const void* __restrict__ bank,
                                                                                       StepArgs a) {
   static_assert(pulses_threads<SDX_KIND_MU, 4>() == 512 && pulses_threads<SDX_KIND_MS, 2>() == 512, "512-thread tiles");
   __shared__ StepLds U;
-  __shared__ int msg_of[64];
+  __shared__ int msg_of[MS_TM_MAX];
   // the ranges in dispatch order (SDX_STEP_ORDER): 0 = MU, MS, MC; 1 = MC, MU, MS; 2 = MU, MC, MS
   constexpr int R0 = SDX_STEP_ORDER == 0 ? 0 : (SDX_STEP_ORDER == 1 ? 2 : 0);
   constexpr int R1 = SDX_STEP_ORDER == 0 ? 1 : (SDX_STEP_ORDER == 1 ? 0 : 2);
@@ -3054,7 +3103,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void k
   if (r == 0) {
     pulses_tile<SDX_KIND_MU, 4, 64, MRU, 0>(bank, a.mu, a.mu_out, w, U.mu, msg_of);
   } else if (r == 1) {
-    ms_tile_by_class<MRS>(bank, a.ms, a.ms_out, w, U.ms2, U.ms4, msg_of);
+    ms_tile_by_class<MRS>(bank, a.ms, a.ms_out, w, a.ms_tm, U.ms, msg_of);
   } else {
     const int half = (int)threadIdx.x >> 8;
     mc_block_c<MC_SHORTW>(bank, a.mc, a.mc_out, 2 * w + half, (int)threadIdx.x & 255, U.mc[half]);
@@ -3224,6 +3273,22 @@ int sdx_fill_async(void* dst, int value, size_t nbytes, void* hip_stream) {
   return SDX_OK;
 }
 
+// Messages per MS workgroup (ms_tile_by_class).  128-message tiles halve the workgroup count, which pays
+// only where the range still fills the device's tile slots several times over (256 CUs x 2 tiles):
+// below SDX_MS_TILE128_MIN messages (stream chunks, small Engine.run batches) the 64-message tiles stay.
+// Measured (k_ms_classes alone, 64 vs 128, DESIGN.md section 4 "128-message MS tiles"): 32k messages 0.075 vs
+// 0.130 ms, 64k 0.124 vs 0.141, 128k 0.207 vs 0.217, 256k 0.374 vs 0.336, 333k 0.467 vs 0.411.
+// SDX_MS_TILE=64|128 overrides the choice; read per call, so a test compares both in one process
+#ifndef SDX_MS_TILE128_MIN
+#define SDX_MS_TILE128_MIN 262144
+#endif
+static int ms_tile_msgs(int n) {
+  const char* e = getenv("SDX_MS_TILE");
+  if (e && e[0] == '6' && e[1] == '4' && !e[2]) return 64;
+  if (e && e[0] == '1' && e[1] == '2' && e[2] == '8' && !e[3]) return 128;
+  return n >= SDX_MS_TILE128_MIN ? 128 : 64;
+}
+
 int sdx_demod_pulses(const sdx_bank* bank, int kind, const sdx_pulse_batch* batch, const sdx_out* out,
                      void* hip_stream) {
   if (!bank || !batch || !out) return fail(SDX_EINVAL, "null argument");
@@ -3242,6 +3307,7 @@ int sdx_demod_pulses(const sdx_bank* bank, int kind, const sdx_pulse_batch* batc
   const sdx_out& o = *out;
   constexpr int TM = 64;
   const int grid = (ntot + TM - 1) / TM;
+  const int ms_tm = kind == SDX_KIND_MS ? ms_tile_msgs(ntot) : TM;  // k_ms_classes: 64 or 128 per workgroup
   const dim3 blk(sdx::pulses_threads<SDX_KIND_MU, 4>());
   static_assert(sdx::pulses_threads<SDX_KIND_MU, 4>() == sdx::pulses_threads<SDX_KIND_MS, 4>(), "one block shape");
   if (kind == SDX_KIND_MU && b.mrec_dev)
@@ -3249,7 +3315,7 @@ int sdx_demod_pulses(const sdx_bank* bank, int kind, const sdx_pulse_batch* batc
   else if (kind == SDX_KIND_MU)
     hipLaunchKernelGGL((sdx::k_pulses<SDX_KIND_MU, 4, 64>), dim3(grid), blk, 0, st, bank->dev, b, o);
   else if (b.mrec_dev && SDX_MS_NARROW)
-    hipLaunchKernelGGL(sdx::k_ms_classes<1>, dim3(grid), blk, 0, st, bank->dev, b, o);
+    hipLaunchKernelGGL(sdx::k_ms_classes<1>, dim3((ntot + ms_tm - 1) / ms_tm), blk, 0, st, bank->dev, b, o, ms_tm);
   else if (b.mrec_dev)
     hipLaunchKernelGGL((sdx::k_pulses<SDX_KIND_MS, 4, 64, 1>), dim3(grid), blk, 0, st, bank->dev, b, o);
   else if (SDX_MS_NARROW) {
@@ -3264,7 +3330,7 @@ int sdx_demod_pulses(const sdx_bank* bank, int kind, const sdx_pulse_batch* batc
       hipLaunchKernelGGL((sdx::k_pulses<SDX_KIND_MS, 2, 64, 0, 1>), dim3(grid), blk, 0, st, bank->dev, b, o);
       hipLaunchKernelGGL((sdx::k_pulses<SDX_KIND_MS, 4, 64, 0, 3>), dim3(grid), blk, 0, st, bank->dev, b, o);
     } else {
-      hipLaunchKernelGGL(sdx::k_ms_classes<0>, dim3(grid), blk, 0, st, bank->dev, b, o);
+      hipLaunchKernelGGL(sdx::k_ms_classes<0>, dim3((ntot + ms_tm - 1) / ms_tm), blk, 0, st, bank->dev, b, o, ms_tm);
     }
   } else
     hipLaunchKernelGGL((sdx::k_pulses<SDX_KIND_MS, 4, 64>), dim3(grid), blk, 0, st, bank->dev, b, o);
@@ -3368,7 +3434,9 @@ int sdx_demod_step(const sdx_bank* bank, const sdx_step* step, void* hip_stream)
       return fail(SDX_EINVAL, "work_cap above 4 GiB - 112 KB: spill offsets are 32-bit");
     a.ms = b;
     a.ms_out = *step->ms_out;
-    a.t_ms = (count(b.n, b.n_sel, b.sel_dev) + 63) / 64;
+    const int nms = count(b.n, b.n_sel, b.sel_dev);
+    a.ms_tm = ms_tile_msgs(nms);
+    a.t_ms = (nms + a.ms_tm - 1) / a.ms_tm;
   }
   if (mc_fused) {
     a.mc = *step->mc;
