@@ -217,6 +217,19 @@ SDX_DEV void wave_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
+// OR over each aligned group of G (8 or 16) lanes, in every lane of the group, by DPP within a row
+// of 16: the quad's other three lanes (quad_perm [1,0,3,2], [2,3,0,1]), the half row's other quad
+// (row_half_mirror), the row's other half (row_mirror).  All lanes of the wave must be active.
+template <int G>
+SDX_DEV uint32_t group_or(uint32_t v) {
+  static_assert(G == 8 || G == 16, "a half row or a row of 16 lanes");
+  v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);
+  v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);
+  v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true);
+  if constexpr (G == 16) v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, true);
+  return v;
+}
+
 SDX_DEV int lanes_below(uint64_t mask) {
   const int l = lane_id();
   return popc64(l ? (mask & ((1ull << l) - 1)) : 0ull);
@@ -1740,7 +1753,17 @@ SDX_DEV void pulses_tile(const void* __restrict__ bank, const sdx_pulse_batch& b
   if constexpr (NW <= 4) {
   // per pass: the lane's 16 characters -> 10 id masks of 16 bits (SWAR on 4 characters per dword),
   // written as 16-bit pieces of the per-id bitmaps; non-digit characters per message by ballot
+  // id-pair presence (L.pairs: bit 10a+b <=> "ab" occurs at some p, p + 1 < n) comes from the same
+  // registers: the lane's 16 characters and the one after them (byte r of the fifth dword, masked by
+  // n like the others) give 16 pair numbers q = 10 c[i] + c[i+1], four per dword by SWAR; a pair with
+  // a character that is no id (non-digit, 0xFE, past n) gets q = 255.  The lane's 100-bit set is
+  // OR-reduced over the message's LPM lanes by DPP and written once per message, with nlen and
+  // digit_ok.  -DSDX_PAIRS_LDS keeps the former pass (lane = pair over the LDS bitmaps, one message
+  // at a time) for A/B.
   uint32_t ndmsg = 0;  // bit k: tile message k of the wave holds a non-digit character
+#ifdef SDX_PROF
+  unsigned long long pair_cy = 0;
+#endif
 #pragma unroll
   for (int ps = 0; ps < SPASS; ++ps) {
     const int k = ps * SMSG + lane / LPM, j = lane % LPM;
@@ -1749,6 +1772,9 @@ SDX_DEV void pulses_tile(const void* __restrict__ bank, const sdx_pulse_batch& b
     const int lo = __shfl((int)(uint32_t)pf_off, k);
     const uint32_t r = (uint32_t)lo & 3u;  // realignment of the message's rows
     uint32_t V = 0, P0 = 0, P1 = 0, P2 = 0, P3 = 0, FE = 0;
+#ifndef SDX_PAIRS_LDS
+    uint32_t l4[5], dgt[5];  // per dword: digit nibbles, byte bit 0 = the character is an id inside the message
+#endif
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       uint32_t c = __builtin_amdgcn_alignbyte(sx[ps][i + 1], sx[ps][i], r);  // bytes r.. of the pair
@@ -1759,6 +1785,10 @@ SDX_DEV void pulses_tile(const void* __restrict__ bank, const sdx_pulse_batch& b
       const uint32_t bad = (t & 0xF0F0F0F0u) | ((lo4 + 0x06060606u) & 0x10101010u);  // byte != 0 <=> not a digit
       const uint32_t nz = ((bad & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | bad;               // bit 7: byte != 0
       const uint32_t dg = (~nz >> 7) & 0x01010101u;                                // byte bit 0: digit
+#ifndef SDX_PAIRS_LDS
+      l4[i] = lo4;
+      dgt[i] = dg;
+#endif
       V |= ((dg * 0x01020408u) >> 24) << (4 * i);
       P0 |= (((lo4 & 0x01010101u) * 0x01020408u) >> 24) << (4 * i);
       P1 |= (((lo4 & 0x02020202u) * 0x00810204u) >> 24) << (4 * i);
@@ -1786,10 +1816,59 @@ SDX_DEV void pulses_tile(const void* __restrict__ bank, const sdx_pulse_batch& b
         row[id * T::WS * 4] = (uint16_t)m;
       }
     }
+#ifndef SDX_PAIRS_LDS
+    {
+#ifdef SDX_PROF
+      const unsigned long long t_p0 = __builtin_amdgcn_s_memtime();
+#endif
+      // the character after the lane's 16: position 16 j + 16, which may lie in a loaded dword and
+      // still belong to the next message (n <= 64 NW, so the message's last lane never has one)
+      const uint32_t ct = ((sx[ps][4] >> (8 * r)) & 0xFFu) ^ 0x30u;
+      l4[4] = ct & 15u;
+      dgt[4] = (ct < 10u && 16 * j + 16 < n) ? 1u : 0u;
+      uint64_t plo = 0, phi = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const uint32_t nx = __builtin_amdgcn_alignbyte(l4[i + 1], l4[i], 1);                // c[p + 1] under c[p]
+        const uint32_t vd = dgt[i] & __builtin_amdgcn_alignbyte(dgt[i + 1], dgt[i], 1);    // both are ids
+        // bytes: 10 c[p] + c[p+1] (<= 15 * 11, no carry between bytes), 0xFF where the pair is none
+        const uint32_t q4 = (l4[i] * 10u + nx) | ((vd ^ 0x01010101u) * 0xFFu);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const uint32_t q = (q4 >> (8 * e)) & 0xFFu;  // 0..99, or 255 -> bit 127 (cleared below)
+          const uint64_t bit = 1ull << (q & 63u);
+          const uint64_t up = 0ull - (uint64_t)((q >> 6) & 1u);
+          plo |= bit & ~up;
+          phi |= bit & up;
+        }
+      }
+      uint32_t pw[4] = {(uint32_t)plo, (uint32_t)(plo >> 32), (uint32_t)phi, (uint32_t)(phi >> 32) & 0xFu};
+#pragma unroll
+      for (int w = 0; w < 4; ++w) pw[w] = group_or<LPM>(pw[w]);
+      if (j == 0 && mi < nvalid) {
+        L.pairs[mi][0] = ((uint64_t)pw[1] << 32) | pw[0];
+        L.pairs[mi][1] = ((uint64_t)pw[3] << 32) | pw[2];
+        L.nlen[mi] = n;
+        L.digit_ok[mi] = (((ndb >> (lane & ~(LPM - 1))) & ((1ull << LPM) - 1)) == 0 && n > 0) ? 1u : 0u;
+      }
+#ifdef SDX_PROF
+      pair_cy += __builtin_amdgcn_s_memtime() - t_p0;
+#endif
+    }
+#endif
   }
   wave_sync();
+#ifdef SDX_PAIRS_LDS
   PROF_ADD(18, t_bm);
   PROF_T(t_pairs);
+#else
+  (void)ndmsg;
+#ifdef SDX_PROF
+  PROF_ADD(18, t_bm + pair_cy);  // the bitmaps' share of the passes
+  const unsigned long long t_pairs = __builtin_amdgcn_s_memtime() - pair_cy;
+#endif
+#endif
+#ifdef SDX_PAIRS_LDS
 #pragma unroll
   for (int k = 0; k < MPW; ++k) {
     const int mi = wave + k * NWAVE;
@@ -1823,6 +1902,7 @@ SDX_DEV void pulses_tile(const void* __restrict__ bank, const sdx_pulse_batch& b
       L.digit_ok[mi] = (nd == 0 && n > 0) ? 1u : 0u;
     }
   }
+#endif
   PROF_ADD(19, t_pairs);
   }
   if constexpr (NW > 4) {  // long variants: one message per wave
