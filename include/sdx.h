@@ -406,6 +406,28 @@ int sdx_parse_floats(const sdx_lines* strs, double* val_dev, uint8_t* cls_dev, v
  * with json_form "NaN" / "Infinity" / "-Infinity".  val_dev and text_dev must be 8-byte aligned. */
 int sdx_format_floats(const double* val_dev, int32_t n, int32_t json_form, uint8_t* text_dev, void* hip_stream);
 
+/* ---- byte-stream input: a transport's read buffer -> sdx_lines.offsets_dev ------------------------
+ * What StreamReader.readline() does (signalduino/transport.py:113-123) for a whole buffer at once.
+ * offsets_dev[0] = 0; for the k-th '\n' (k = 0, 1, ...) at byte p_k, k < cap: offsets_dev[k + 1] = p_k + 1,
+ * so a line keeps its terminator (sdx_parse_lines strips it) and an empty line is a line.
+ * final != 0 and bytes left after the last '\n': they form one more line (its offset = nbytes), as
+ * readline() returns the rest at EOF (transport.py:118).
+ * count_dev[0] = lines found (also when > cap: nothing past offsets_dev[cap] is written),
+ * count_dev[1] = start of the unterminated tail (= nbytes when there is none or it became a line).
+ * bytes_dev as sdx_lines.bytes_dev: 8-byte aligned and readable 16 bytes past nbytes; bytes at or after
+ * nbytes are never counted.  offsets_dev [cap + 1] and count_dev [2] 8-byte aligned; scratch_dev holds
+ * sdx_split_work_bytes(nbytes) bytes (one int32 per SDX_SPLIT_SPAN bytes, at least one).  nbytes in
+ * [0, 2^31), cap >= 0, no null pointer: otherwise SDX_EINVAL before any HIP call.  Two kernels on the
+ * caller's stream; no allocation, no synchronisation. */
+#define SDX_SPLIT_SPAN 16384
+size_t sdx_split_work_bytes(int64_t nbytes);
+/* host side, no GPU call: how many of host[0, n) equal `value`.  A caller that cuts a byte stream into
+ * chunks counts each chunk's '\n's with it before the bytes go up, so it can size the chunk's launches
+ * without waiting for count_dev (and compare the two afterwards). */
+uint64_t sdx_host_count_byte(const uint8_t* host, uint64_t n, int value);
+int sdx_split_lines(const uint8_t* bytes_dev, int64_t nbytes, int32_t final, int64_t* offsets_dev, int32_t cap,
+                    int64_t* count_dev, int32_t* scratch_dev, void* hip_stream);
+
 /* ---- publish-ready JSON ------------------------------------------------------
  * The MQTT publication of a DecodedMessage, MqttPublisher._message_to_json (signalduino/mqtt.py:
  * 227-245): json.dumps(asdict(message) minus "raw", indent=4), i.e.

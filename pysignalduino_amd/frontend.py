@@ -97,14 +97,25 @@ class LineBatch:
 
     def __init__(self, eng: "runtime.Engine", data: np.ndarray, offsets: np.ndarray):
         t = eng.torch
+        # 16 bytes of padding: the kernel reads whole aligned 8-byte words (include/sdx.h)
+        self._alloc(eng, t.from_numpy(np.concatenate([data, np.zeros(16, np.uint8)])).to(eng.dev),
+                    t.from_numpy(offsets).to(eng.dev), len(offsets) - 1, int(offsets[-1]))
+
+    @classmethod
+    def from_device(cls, eng: "runtime.Engine", bytes_dev, offsets_dev, n: int, total: int) -> "LineBatch":
+        """A batch over lines already on the device: ``bytes_dev`` (uint8, 16 readable bytes past
+        ``total``) and ``offsets_dev`` (int64[n + 1], offsets[n] = total), e.g. what sdx_split_lines wrote."""
+        lb = cls.__new__(cls)
+        lb._alloc(eng, bytes_dev, offsets_dev, int(n), int(total))
+        return lb
+
+    def _alloc(self, eng: "runtime.Engine", bytes_dev, offsets_dev, n: int, total: int) -> None:
+        t = eng.torch
         d = eng.dev
-        n = len(offsets) - 1
-        total = int(offsets[-1])
         self.n = n
         self.eng = eng
-        # 16 bytes of padding: the kernel reads whole aligned 8-byte words (include/sdx.h)
-        self.bytes = t.from_numpy(np.concatenate([data, np.zeros(16, np.uint8)])).to(d)
-        self.offsets = t.from_numpy(offsets).to(d)
+        self.bytes = bytes_dev
+        self.offsets = offsets_dev
         e = lambda k, dt: t.empty(max(k, 1), dtype=dt, device=d)  # noqa: E731
         self.kind, self.status = e(n, t.uint8), e(n, t.uint8)
         self.slot = t.empty(3 * total + 16, dtype=t.uint8, device=d)
@@ -242,6 +253,33 @@ def pack_lines(lines: Sequence[Union[str, bytes]], copy: bool = True):
     return (data.copy() if copy else data), offsets, bad
 
 
+class _LinesView:
+    """The lines of a split byte buffer as a read-only sequence: line i = raw[offsets[i]: offsets[i + 1]]
+    (with its terminator), sliced on demand -- no list of a million bytes objects."""
+
+    def __init__(self, raw, offsets: np.ndarray):
+        self.raw, self.offsets = raw, offsets
+
+    def __len__(self) -> int:
+        return len(self.offsets) - 1
+
+    def __getitem__(self, i: int) -> bytes:
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        return bytes(self.raw[int(self.offsets[i]): int(self.offsets[i + 1])])
+
+
+def lines_of(data: bytes, final: bool = True):
+    """What the byte-stream entries take as the lines of ``data``: data.split(b"\\n") without its last
+    element when that is empty or ``final`` is false -> (lines, tail); the tail is b"" unless final is false."""
+    parts = bytes(data).split(b"\n")
+    last = parts.pop()
+    if final and last:
+        parts.append(last)
+        last = b""
+    return parts, last
+
+
 class SignalParser:
     """signalduino/parser/__init__.py:18-77 with the whole line -> DecodedMessage path on the GPU."""
 
@@ -274,13 +312,17 @@ class SignalParser:
         """Batch form of parse_line: one upload, one parse launch, one launch per demodulation
         variant, one read-back.  Returns one DecodedMessage list per line (or the ContractError
         for a line outside the device contract)."""
-        n = len(lines)
-        if n == 0:
+        if len(lines) == 0:
             return []
         data, offsets, bad = pack_lines(lines)
+        return self._objects(lines, LineBatch(self.protocols._ensure(), data, offsets), offsets, bad, len(data))
+
+    def _objects(self, lines, lb: LineBatch, offsets: np.ndarray, bad: dict, nbytes: int):
+        """parse_lines from the uploaded batch on: ``lines`` indexable (lines[i] = line i's text),
+        ``offsets`` the host copy of lb.offsets, ``nbytes`` = offsets[n]."""
+        n = len(lines)
         eng = self.protocols._ensure()
         bk = self.protocols._bank
-        lb = LineBatch(eng, data, offsets)
         lb.launch()
         sels, cnt = lb.selections()
         res = {}
@@ -299,7 +341,7 @@ class SignalParser:
             nmn = int(cnt[runtime.SEL_MN])
             res["MN"] = eng.run(runtime.KIND_MN, lb.mn_batch(), sel_short=sels[runtime.SEL_MN],
                                 mn_elig=self.protocols.mn_eligibility(self.rfmode),
-                                rec_cap=len(bk.mn_pids) * nmn + 1024, heap_cap=int(4 * len(data) + 64 * nmn + 65536))
+                                rec_cap=len(bk.mn_pids) * nmn + 1024, heap_cap=int(4 * nbytes + 64 * nmn + 65536))
         # read-back of the per-line fields the Python objects need
         kind = lb.kind[:n].cpu().numpy()
         status = lb.status[:n].cpu().numpy()
@@ -474,13 +516,16 @@ class SignalParser:
         ``MqttPublisher._message_to_json(parse_line(line)[0])`` (signalduino/controller.py:254-257,
         mqtt.py:227-245), or None when the line decodes to nothing -- parse, demodulation and JSON
         serialisation (sdx_serialize_json) all on the device; only the texts come back."""
-        n = len(lines)
-        if n == 0:
+        if len(lines) == 0:
             return []
         data, offsets, bad = pack_lines(lines)
+        return self._texts(lines, LineBatch(self.protocols._ensure(), data, offsets), bad, len(data))
+
+    def _texts(self, lines, lb: LineBatch, bad: dict, nbytes: int):
+        """parse_lines_json from the uploaded batch on (``lines`` and ``nbytes`` as in _objects)."""
+        n = len(lines)
         eng = self.protocols._ensure()
         bk = self.protocols._bank
-        lb = LineBatch(eng, data, offsets)
         lb.launch()
         sels, cnt = lb.selections()
         lo = {"meta": lb.meta, "pat_val": lb.pat_val, "cp_slot": lb.cp_slot}
@@ -500,8 +545,8 @@ class SignalParser:
                          [(lb.mc_batch(), mc_sel, False)]))
         if cnt[runtime.SEL_MN]:
             k = int(cnt[runtime.SEL_MN])
-            jobs.append((runtime.KIND_MN, len(bk.mn_pids) * k + 1024, int(4 * len(data) + 64 * k + 65536),
-                         int(6 * len(data) + 400 * k + 65536), [(lb.mn_batch(), sels[runtime.SEL_MN], False)]))
+            jobs.append((runtime.KIND_MN, len(bk.mn_pids) * k + 1024, int(4 * nbytes + 64 * k + 65536),
+                         int(6 * nbytes + 400 * k + 65536), [(lb.mn_batch(), sels[runtime.SEL_MN], False)]))
         elig = self.protocols.mn_eligibility(self.rfmode)
         texts: List[Any] = [None] * n
         host_rows: List[int] = []   # lines whose text is built from parse_lines' objects (general paths)
@@ -563,6 +608,48 @@ class SignalParser:
                 texts[i] = ContractError(f"line {i} is outside the device contract of the front end "
                                          f"(kind {_KIND_NAME.get(int(kinds[i]), '?')})")
         return texts
+
+    # -- byte-stream input ---------------------------------------------------------------------------
+    def parse_bytes(self, data, final: bool = True):
+        """parse_lines over a transport's raw read buffer (bytes-like): the bytes are uploaded and split
+        into lines on the device (sdx_split_lines: every '\\n' ends a line, as StreamReader.readline(),
+        signalduino/transport.py:113-123).  ``final=True``: bytes after the last '\\n' are the last line
+        (readline() at EOF); returns parse_lines' list for those lines.  ``final=False``: returns
+        (that list for the terminated lines, the unterminated tail as bytes) -- prepend the tail to the
+        next buffer."""
+        lines, lb, tail = self._split_bytes(data, final)
+        out = self._objects(lines, lb, lines.offsets, {}, int(lines.offsets[-1])) if len(lines) else []
+        return out if final else (out, tail)
+
+    def parse_bytes_json(self, data, final: bool = True):
+        """parse_lines_json over a raw read buffer (see parse_bytes; the same return forms)."""
+        lines, lb, tail = self._split_bytes(data, final)
+        out = self._texts(lines, lb, {}, int(lines.offsets[-1])) if len(lines) else []
+        return out if final else (out, tail)
+
+    def _split_bytes(self, data, final: bool):
+        """Upload + sdx_split_lines -> (the lines as a host view, their LineBatch or None, the tail)."""
+        raw = data if isinstance(data, (bytes, bytearray)) else bytes(data)
+        nb = len(raw)
+        if nb >= 1 << 31:
+            raise ValueError("parse_bytes takes less than 2^31 bytes per call")
+        eng = self.protocols._ensure()
+        t, d = eng.torch, eng.dev
+        bytes_dev = t.zeros(nb + 16, dtype=t.uint8, device=d)   # 16 zero bytes of read-ahead (include/sdx.h)
+        if nb:
+            bytes_dev[:nb] = t.from_numpy(np.frombuffer(raw, np.uint8).copy())
+        cap = raw.count(b"\n") + 1          # room for every line; the launches are sized by the device's count
+        offsets_dev = t.empty(cap + 1, dtype=t.int64, device=d)
+        count = t.zeros(2, dtype=t.int64, device=d)
+        scratch = t.empty(eng.split_work_ints(nb), dtype=t.int32, device=d)
+        eng.split_lines(bytes_dev, nb, final, offsets_dev, cap, count, scratch)
+        n, tail_at = (int(x) for x in count.cpu().numpy())
+        if n > cap:
+            raise RuntimeError(f"sdx_split_lines found {n} lines, the host at most {cap}")
+        offsets = offsets_dev[: n + 1].cpu().numpy()
+        lines = _LinesView(raw, offsets)
+        lb = LineBatch.from_device(eng, bytes_dev, offsets_dev, n, int(offsets[-1])) if n else None
+        return lines, lb, bytes(raw[tail_at:])
 
     @staticmethod
     def _meta_str(m: np.ndarray, base: int) -> Optional[str]:

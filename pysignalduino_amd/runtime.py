@@ -46,7 +46,8 @@ EXPORTED = ["sdx_abi_version", "sdx_last_error", "sdx_source_hash", "sdx_layout_
             "sdx_exchange_unpack", "sdx_pulses_work_bytes", "sdx_group_work_bytes", "sdx_group_pulses",
             "sdx_general_work_bytes", "sdx_demod_pulses_general", "sdx_mc_general_work_bytes", "sdx_demod_mc_general",
             "sdx_lines_general", "sdx_lines_exact", "sdx_parse_floats", "sdx_format_floats", "sdx_copy_async", "sdx_copy_async_kind", "sdx_copy_async_narrow",
-            "sdx_fill_async", "sdx_demod_step", "sdx_group_step"]
+            "sdx_fill_async", "sdx_demod_step", "sdx_group_step", "sdx_split_work_bytes", "sdx_split_lines",
+            "sdx_host_count_byte"]
 GROUP_MIN = int(os.environ.get("SDX_GROUP_MIN", "4096"))   # SDX_GROUP_MIN (the env: A/B of the grouping)
 
 
@@ -217,6 +218,12 @@ def load_library(path: Optional[str] = None):
     lib.sdx_parse_floats.restype = c_int
     lib.sdx_format_floats.argtypes = [c_void_p, c_int32, c_int32, c_void_p, c_void_p]
     lib.sdx_format_floats.restype = c_int
+    lib.sdx_split_work_bytes.argtypes = [ctypes.c_int64]
+    lib.sdx_split_work_bytes.restype = c_size_t
+    lib.sdx_split_lines.argtypes = [c_void_p, ctypes.c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]
+    lib.sdx_split_lines.restype = c_int
+    lib.sdx_host_count_byte.argtypes = [c_void_p, ctypes.c_uint64, c_int]
+    lib.sdx_host_count_byte.restype = ctypes.c_uint64
     lib.sdx_demod_mc.argtypes = [c_void_p, POINTER(SdxMcBatch), POINTER(SdxOut), c_void_p]
     lib.sdx_group_step.restype = c_int
     lib.sdx_group_step.argtypes = [c_void_p, POINTER(SdxGroupJob), POINTER(SdxGroupJob), c_void_p]
@@ -634,6 +641,23 @@ class Engine:
                        0 if sel is None else int(sel.numel()), elig, method, 0)
         o = self._out_struct(out)
         _check(self.lib, self.lib.sdx_demod_mn(self.handle, ctypes.byref(b), ctypes.byref(o), self.stream_ptr()))
+
+    def split_work_ints(self, nbytes: int) -> int:
+        """int32 entries of sdx_split_lines' scratch for a buffer of nbytes."""
+        return int(self.lib.sdx_split_work_bytes(int(nbytes))) // 4
+
+    def split_lines(self, bytes_t, nbytes: int, final: bool, offsets_t, cap: int, count_t, scratch_t, stream=None) -> None:
+        """sdx_split_lines on ``stream`` (default: the current one; no host sync): the '\\n'-terminated
+        lines of bytes_t[:nbytes] -> offsets_t[: cap + 1] (int64), count_t (int64[2]: lines found, start of
+        the unterminated tail).  bytes_t holds 16 readable bytes past nbytes."""
+        nbytes, cap = int(nbytes), int(cap)
+        if (bytes_t.numel() < nbytes + 16 or offsets_t.numel() * offsets_t.element_size() < 8 * (cap + 1) or
+                count_t.numel() * count_t.element_size() < 16 or
+                scratch_t.numel() * scratch_t.element_size() < 4 * self.split_work_ints(max(nbytes, 0))):
+            raise ValueError("split_lines: a buffer is too small for nbytes / cap")
+        st = self.stream_ptr() if stream is None else c_void_p(stream.cuda_stream)
+        _check(self.lib, self.lib.sdx_split_lines(_ptr(bytes_t), nbytes, 1 if final else 0, _ptr(offsets_t), cap,
+                                                  _ptr(count_t), _ptr(scratch_t), st))
 
     def launch_json(self, kind: int, demod_out, lines_out, n: int, jout, first_only: bool = True) -> None:
         """sdx_serialize_json over a demodulation launch's device outputs (no host sync).  first_only:

@@ -23,6 +23,12 @@ so the GPU always has a chunk queued behind the one it runs.  Lines the fast pat
 messages whose results overflowed their buffers (MC frames of > 128 hex characters, ST_OVF_*) --
 are taken by ``SignalParser.parse_lines_json`` / ``parse_lines`` on those lines only, so every
 line's result is exactly the batch API's.
+
+``submit_bytes`` takes a transport's read buffer as it was read (the reference splits it with
+StreamReader.readline(), signalduino/transport.py:113-123): stage A then uploads the bytes only and
+runs sdx_split_lines in front of the parse, which writes the offsets on the device; the host cuts the
+buffer at line ends into chunks (cut_bytes: rfind + a count, no Python loop over bytes), carries the
+unterminated tail into the next call, and gets the chunk's offsets back in stage C.
 """
 from __future__ import annotations
 
@@ -46,6 +52,97 @@ _GROUP2 = os.environ.get("SDX_STREAM_GROUP2", "1") != "0"   # A/B: one sdx_group
 _MC_SEP = os.environ.get("SDX_STREAM_MC_SEP") == "1"   # A/B: MC's short class in its own launch
 
 
+class _NlView:
+    """rfind / find / count of b"\\n" over a numpy uint8 array, with bytes' signatures: what cut_bytes
+    needs of a buffer that is no bytes object (a pinned tensor's memory, a memoryview)."""
+
+    BLOCK = 1 << 16
+    PART = 1 << 20      # count(): what one thread takes at a time
+    _pool = None
+
+    def __init__(self, a: np.ndarray):
+        if not a.flags.c_contiguous:
+            raise ValueError("a contiguous uint8 buffer")
+        self.a = a
+        self.ptr = a.ctypes.data
+        self.lib = runtime.load_library()
+
+    def __len__(self) -> int:
+        return len(self.a)
+
+    def _count(self, lo: int, hi: int) -> int:
+        return int(self.lib.sdx_host_count_byte(self.ptr + lo, hi - lo, 10)) if hi > lo else 0
+
+    def count(self, _nl, lo: int, hi: int) -> int:
+        """A chunk's count is the host's one pass over every byte (sdx_host_count_byte, a vectorised C
+        loop); large ranges go over a few threads (ctypes releases the GIL), 1 MB parts each."""
+        if hi - lo <= 2 * self.PART:
+            return self._count(lo, hi)
+        if _NlView._pool is None:
+            from concurrent.futures import ThreadPoolExecutor
+            _NlView._pool = ThreadPoolExecutor(max_workers=8, thread_name_prefix="sdx-nl")
+        return sum(_NlView._pool.map(lambda s: self._count(s, min(hi, s + self.PART)), range(lo, hi, self.PART)))
+
+    def rfind(self, _nl, lo: int, hi: int) -> int:
+        while hi > lo:      # from the back, a block at a time: the last newline is near the end
+            b = max(lo, hi - self.BLOCK)
+            hit = np.flatnonzero(self.a[b:hi] == 10)
+            if len(hit):
+                return b + int(hit[-1])
+            hi = b
+        return -1
+
+    def find(self, _nl, lo: int, hi: int) -> int:
+        while lo < hi:
+            e = min(hi, lo + self.BLOCK)
+            hit = np.flatnonzero(self.a[lo:e] == 10)
+            if len(hit):
+                return lo + int(hit[0])
+            lo = e
+        return -1
+
+
+def cut_bytes(view, lo: int, carry_len: int, C: int, B: int) -> Tuple[int, int]:
+    """The next chunk of a byte buffer: (hi, n) such that view[lo:hi] ends on a '\\n' (or hi == lo: no
+    line ends in reach), holds n <= C newlines and, behind a carried line start of ``carry_len`` bytes,
+    fits B bytes.  ``view``: bytes-like with rfind / find / count (the host never walks the bytes in
+    Python).  A line that cannot fit B bytes raises ValueError."""
+    N = len(view)
+    room = B - carry_len
+    hi = view.rfind(b"\n", lo, min(N, lo + max(room, 0))) + 1
+    if hi <= lo:
+        if N - lo > room:
+            raise ValueError(f"a line of more than {B} bytes (the stream's chunk_bytes)")
+        return lo, 0         # only an unterminated tail is left
+    n = view.count(b"\n", lo, hi)
+    while n > C:             # too many lines: halve the piece and try again
+        h2 = view.rfind(b"\n", lo, lo + (hi - lo) // 2) + 1
+        if h2 <= lo:         # the first line alone is longer than half the piece
+            h2 = view.find(b"\n", lo, hi) + 1
+        hi = h2
+        n = view.count(b"\n", lo, hi)
+    return hi, n
+
+
+class _ChunkBytes:
+    """The raw bytes of a submit_bytes chunk on the host: the carried line start + the piece of the
+    caller's buffer (or of the slot's pinned buffer), never joined."""
+
+    def __init__(self, carry: np.ndarray, body: np.ndarray):
+        self.carry, self.body = carry, body
+
+    def slice(self, a: int, b: int) -> bytes:
+        c = len(self.carry)
+        if a >= c:
+            return self.body[a - c: b - c].tobytes()
+        if b <= c:
+            return self.carry[a:b].tobytes()
+        return self.carry[a:].tobytes() + self.body[: b - c].tobytes()
+
+    def copy(self) -> "_ChunkBytes":
+        return _ChunkBytes(self.carry.copy(), self.body.copy())
+
+
 class ChunkResult:
     """One chunk's results in host memory.  json output: ``texts()`` -> per line the MQTT text the
     reference publishes for it (``_message_to_json(parse_line(line)[0])``), None (nothing decoded) or
@@ -65,11 +162,32 @@ class ChunkResult:
         self.wire = self.layout = None
         self.host = {}            # line -> result of the batch API (fallback lines)
         self.affix = {}
+        # the chunk's text, for line(i): the submitted sequence, or packed (data, offsets), or a
+        # submit_bytes chunk's bytes (_ChunkBytes) + the device's offsets
+        self.src_lines = self.src_data = self.src_offsets = None
+
+    def line(self, i: int) -> bytes:
+        """The raw bytes of line i as submitted (a submit_bytes line keeps its terminator)."""
+        if not 0 <= i < self.n:
+            raise IndexError(i)
+        if self.src_lines is not None:
+            ln = self.src_lines[i]
+            return ln.encode("latin-1") if isinstance(ln, str) else bytes(ln)
+        a, b = int(self.src_offsets[i]), int(self.src_offsets[i + 1])
+        if isinstance(self.src_data, _ChunkBytes):
+            return self.src_data.slice(a, b)
+        d = self.src_data.numpy() if hasattr(self.src_data, "numpy") else self.src_data
+        return d[a:b].tobytes()
+
+    def lines(self) -> List[bytes]:
+        return [self.line(i) for i in range(self.n)]
 
     def detach(self) -> "ChunkResult":
         if self.slot is None:
             return self
         self.slot = None
+        if isinstance(self.src_data, _ChunkBytes):   # views of the slot's or the caller's pinned memory
+            self.src_data, self.src_offsets = self.src_data.copy(), self.src_offsets.copy()
         for f in ("kind", "status", "off", "len", "wire"):
             v = getattr(self, f)
             if isinstance(v, np.ndarray):
@@ -167,6 +285,7 @@ class _Slot:
         self.n = 0
         self.lines = None
         self.ev = None
+        self.src = None           # a submit_bytes chunk: its _ChunkBytes (the offsets come back in stage C)
 
 
 class LineStream:
@@ -176,7 +295,9 @@ class LineStream:
     GPU (slots = lag + 1).
 
     submit(lines) -> chunk id; ``submit_packed(data, offsets)`` the same for lines already packed as
-    (uint8 bytes, int64 offsets[n + 1]); poll() -> the finished chunks' ChunkResults in submission
+    (uint8 bytes, int64 offsets[n + 1]); ``submit_bytes(buf)`` -> chunk ids for a transport's raw read
+    buffer (split into lines on the device, the tail carried to the next call); poll() -> the finished
+    chunks' ChunkResults in submission
     order (never blocks on a chunk newer than ``lag`` submits); drain() -> all of them (blocks)."""
 
     def __init__(self, parser, chunk_lines: int = 250_000, chunk_bytes: Optional[int] = None, output: str = "json",
@@ -212,6 +333,7 @@ class LineStream:
         self.elig = parser.protocols.mn_eligibility(parser.rfmode)
         self.h2d_bytes = self.d2h_bytes = 0
         self.kernel_events = []   # (parse start, parse end, demod start, demod end) per chunk
+        self._carry = bytearray()  # submit_bytes: the unterminated tail of the calls so far
 
     # -- public ------------------------------------------------------------------------------------------
     def submit(self, lines: Sequence[Union[str, bytes]]) -> int:
@@ -227,20 +349,72 @@ class LineStream:
         if n > self.C or int(offsets[-1] - offsets[0]) > self.B:
             raise ValueError(f"chunk of {n} lines / {int(offsets[-1] - offsets[0])} bytes exceeds the stream's "
                              f"capacity ({self.C} lines, {self.B} bytes)")
+        s = self._take_slot(n)
+        s.lines, s.bad = lines, bad or {}
+        s.data, s.offsets = data, offsets
+        self._stage_a(s, data, offsets)
+        return self._queued(s)
+
+    def _take_slot(self, n: int) -> _Slot:
         while len(self.inflight) >= len(self.slots):     # every slot busy: finish the oldest chunk
             self._advance(self.inflight[0], 4)
         s = next(x for x in self.slots if x.stage == 0)
+        for r in self.done:     # a byte chunk's result not handed out yet views this slot's input buffers
+            if r.slot is s and isinstance(r.src_data, _ChunkBytes):
+                r.detach()
         s.cid, s.n = self.next_id, n
-        s.lines, s.bad = lines, bad or {}
-        s.data, s.offsets = data, offsets
         self.next_id += 1
-        self._stage_a(s, data, offsets)
+        return s
+
+    def _queued(self, s: _Slot) -> int:
         self.inflight.append(s)
         # the chunks behind: stage B for the previous one, C for the one before, collect the oldest
         for age, want in ((1, 2), (2, 3), (3, 4)):
             if len(self.inflight) > age and self.lag >= age:
                 self._advance(self.inflight[-1 - age], want)
         return s.cid
+
+    def submit_bytes(self, buf, final: bool = False) -> List[int]:
+        """A transport's read buffer, raw: ``buf`` is bytes-like (copied into the slot's pinned buffer) or
+        a PINNED torch uint8 tensor (uploaded from where it is: keep it unchanged until its chunks have
+        been collected), of any size.  Every '\\n' ends a line (StreamReader.readline(),
+        signalduino/transport.py:113-123); the lines are found on the device (sdx_split_lines), the host
+        only cuts the buffer at line ends into chunks within ``chunk_lines`` / ``chunk_bytes`` (cut_bytes).
+        The unterminated tail is carried into the next call; ``final=True`` (or close_bytes()) makes a
+        non-empty tail the last line.  Returns the ids of the chunks queued (none, one or several).  A
+        line longer than ``chunk_bytes`` raises ValueError: the chunks cut in front of it stay queued, the
+        line and what follows it in ``buf`` are not taken."""
+        t = self.torch
+        if isinstance(buf, (bytes, bytearray)):
+            arr = np.frombuffer(buf, np.uint8)
+            view = buf if len(buf) <= 2 * _NlView.PART else _NlView(arr)   # a read buffer: bytes' own rfind / count
+        else:
+            arr = buf.numpy() if isinstance(buf, t.Tensor) else np.frombuffer(memoryview(buf).cast("B"), np.uint8)
+            view = _NlView(arr)
+        pinned = isinstance(buf, t.Tensor) and buf.is_pinned()
+        N, lo, ids = len(arr), 0, []
+        while True:
+            hi, n = cut_bytes(view, lo, len(self._carry), self.C, self.B)
+            if hi == lo:
+                break
+            ids.append(self._submit_piece(buf if pinned else None, arr, lo, hi, n, False))
+            lo = hi
+        self._carry += arr[lo:N].tobytes()     # short: less than one line
+        if final and self._carry:
+            ids.append(self._submit_piece(None, arr, N, N, 1, True))
+        return ids
+
+    def close_bytes(self) -> List[int]:
+        """End of the byte stream: a carried tail becomes the last line (submit_bytes(b"", final=True))."""
+        return self.submit_bytes(b"", final=True)
+
+    def _submit_piece(self, pinned_buf, arr: np.ndarray, lo: int, hi: int, n: int, final: bool) -> int:
+        carry, self._carry = self._carry, bytearray()
+        s = self._take_slot(n)
+        s.lines, s.bad = None, {}
+        s.data = s.offsets = None
+        self._stage_a_bytes(s, np.frombuffer(bytes(carry), np.uint8), pinned_buf, arr, lo, hi, final)
+        return self._queued(s)
 
     def poll(self) -> List[ChunkResult]:
         for s in list(self.inflight):      # stages B and C of any chunk whose previous stage is done
@@ -308,10 +482,64 @@ class LineStream:
         s.parse_ev, s.ev, s.kt = e1, ev, [e0, e1]
         s.stage = 1
 
+    def _stage_a_bytes(self, s: _Slot, carry: np.ndarray, pinned_buf, arr: np.ndarray, lo: int, hi: int, final: bool):
+        """Stage A of a submit_bytes chunk: carry + arr[lo:hi] H2D (no offsets: sdx_split_lines writes them
+        on the device, in front of the parse), the split's count D2H beside the class counts.  The host
+        knows the chunk's n (cut_bytes), so the parse is sized without waiting for the device."""
+        t, lb, n = self.torch, s.lb, s.n
+        cl, m = len(carry), hi - lo
+        nb = cl + m
+        if not hasattr(s, "d_split"):   # the split's buffers, on the slot's first byte chunk
+            s.d_split = t.zeros(2, dtype=t.int64, device=self.eng.dev)
+            s.h_split = t.zeros(2, dtype=t.int64).pin_memory()
+            s.split_scratch = t.empty(self.eng.split_work_ints(self.B), dtype=t.int32, device=self.eng.dev)
+        hb = s.h_bytes.numpy()
+        hb[:cl] = carry
+        if pinned_buf is None:
+            hb[cl:nb] = arr[lo:hi]
+            hb[nb: nb + 16] = 0
+            s.src = _ChunkBytes(hb[:0], hb[:nb])
+        else:
+            s.src = _ChunkBytes(hb[:cl], arr[lo:hi])
+        with t.cuda.stream(self.cin):
+            if pinned_buf is None:
+                runtime.copy_async(lb.bytes[: nb + 16], s.h_bytes[: nb + 16], self.cin)
+            else:   # the piece straight from the caller's pinned buffer, the carried line start in front of it
+                if cl:
+                    runtime.copy_async(lb.bytes[:cl], s.h_bytes[:cl], self.cin)
+                lb.bytes[cl:nb].copy_(pinned_buf[lo:hi], non_blocking=True)
+                runtime.fill_async(lb.bytes[nb: nb + 16], self.cin)
+            h2d = t.cuda.Event()
+            h2d.record(self.cin)
+        self.h2d_bytes += nb
+        lb.n = n
+        lb.c_lines.n = n
+        with t.cuda.stream(self.sp):
+            self.sp.wait_event(h2d)
+            e0, e1 = t.cuda.Event(enable_timing=True), t.cuda.Event(enable_timing=True)
+            e0.record(self.sp)
+            # cap = the host's n: a device count above it writes nothing past offsets[n]; one below it
+            # leaves older offsets of this slot behind (all within the slot's buffers) -- either way the
+            # counts differ and stage B raises
+            self.eng.split_lines(lb.bytes, nb, final, lb.offsets, n, s.d_split, s.split_scratch, self.sp)
+            lb.launch()
+            e1.record(self.sp)
+            runtime.copy_async(s.h_cnt, lb.counts, self.sp)
+            runtime.copy_async(s.h_split, s.d_split, self.sp)
+            ev = t.cuda.Event()
+            ev.record(self.sp)
+        s.parse_ev, s.ev, s.kt = e1, ev, [e0, e1]
+        s.stage = 1
+
     def _stage_b(self, s: _Slot):
         """The demodulation + serialisation launches, sized by the class counts (on the host by now)."""
         t, eng = self.torch, self.eng
         s.ev.synchronize()
+        if s.src is not None and int(s.h_split.numpy()[0]) != s.n:
+            dn, hn, cid = int(s.h_split.numpy()[0]), s.n, s.cid
+            self.inflight.remove(s)     # the chunk is dropped: its offsets are not the host's lines
+            s.reset()
+            raise RuntimeError(f"chunk {cid}: sdx_split_lines found {dn} lines, the host counted {hn}")
         cnt = s.h_cnt.numpy()[: runtime.SEL_NCLASS].astype(np.int64)
         start = np.concatenate([[0], np.cumsum(cnt)])
         lb, n = s.lb, s.n
@@ -425,6 +653,9 @@ class LineStream:
             runtime.copy_async(ho[b: b + n], lb.kind[:n], self.cout)
             runtime.copy_async(ho[b + n: b + 2 * n], lb.status[:n], self.cout)
             s.kb = b
+            if s.src is not None:   # a submit_bytes chunk: the offsets the device found, for line(i)
+                runtime.copy_async(s.h_offs[: n + 1], lb.offsets[: n + 1], self.cout)
+                self.d2h_bytes += 8 * (n + 1)
             ev = t.cuda.Event()
             ev.record(self.cout)
         self.d2h_bytes += b + 2 * n
@@ -439,6 +670,9 @@ class LineStream:
         status = ho[b + n: b + 2 * n]
         r = ChunkResult(s.cid, n, kind, status)
         r.slot = s
+        if s.src is not None:
+            s.data, s.offsets = s.src, s.h_offs.numpy()[: n + 1]
+        r.src_lines, r.src_data, r.src_offsets = s.lines, s.data, s.offsets
         self.kernel_events.append(tuple(s.kt))
         names = list(s.outs)
         redo_kinds = {names[j] for j in range(len(names)) if s.dcur[j, 2]}   # ST_OVF_* in that launch
@@ -480,5 +714,7 @@ class LineStream:
     def _line(s: _Slot, i: int):
         if s.lines is not None:
             return s.lines[i]
+        if isinstance(s.data, _ChunkBytes):
+            return s.data.slice(int(s.offsets[i]), int(s.offsets[i + 1]))
         d = s.data.numpy() if hasattr(s.data, "numpy") else s.data   # a pinned torch tensor or numpy
         return d[int(s.offsets[i]): int(s.offsets[i + 1])].tobytes()

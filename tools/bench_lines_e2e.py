@@ -12,7 +12,12 @@ pinned host memory), beside the kernels' own time per chunk, the PCIe bytes each
 streams the MQTT texts (what BatchingParserTask publishes) instead of the wire form.  --check
 compares chunk 0's results with SignalParser.parse_lines / parse_lines_json on the same lines.
 
-usage: python tools/bench_lines_e2e.py [--lines 1000000 --chunk 250000 --passes 4 --output wire --check]
+``--bytes`` feeds the same corpus as a transport delivers it: one raw byte string per pass (the lines, each
+with the firmware's newline, one after another) in pinned memory, handed to ``LineStream.submit_bytes`` in
+pieces of a chunk's share of the bytes (they end mid-line: the tail is carried) -- the lines are found on the
+device (sdx_split_lines) and no offsets go up over PCIe.  There --check compares the first --chunk lines' results with the packed mode's.
+
+usage: python tools/bench_lines_e2e.py [--lines 1000000 --chunk 250000 --passes 4 --output wire --bytes --check]
 """
 from __future__ import annotations
 
@@ -45,6 +50,48 @@ def copy_rates(torch, host_bytes):
     return rates[0], rates[1]
 
 
+def per_line(results, bank):
+    """Per line of the chunks: json -> its text (or the exception's type); wire -> kind, status and the
+    (protocol id, payload) list of its records (or of the batch API's objects for the lines it took)."""
+    rows = []
+    for r in results:
+        if r.json is not None:
+            rows += [type(t) if isinstance(t, Exception) else t for t in r.texts()]
+            continue
+        pid = {"MU": bank.mu_pids, "MS": bank.ms_pids, "MC": bank.mc_pids, "MN": bank.mn_pids}
+        out = [[int(k), int(s)] for k, s in zip(r.kind.tolist(), r.status.tolist())]
+        for j, nm in enumerate(r.names):
+            d, rec, heap = r.decode(j)
+            hs = heap.tobytes().decode("latin-1")
+            for i in np.nonzero(d["n_rec"])[0].tolist():
+                b, k = int(d[i]["rec_begin"]), int(d[i]["n_rec"])
+                out[i] += [(str(pid[nm][int(x["proto"])]), hs[int(x["payload_off"]): int(x["payload_off"]) + int(x["payload_len"])])
+                           for x in rec[b: b + k]]
+        for i, h in r.host.items():
+            out[i] = out[i][:2] + ([type(h)] if isinstance(h, Exception) else [(m.protocol_id, m.payload) for m in h])
+        rows += out
+    return rows
+
+
+def check_bytes(sp, chunk0, head, C, output, lag):
+    """--bytes --check: the first C lines' results against the packed mode's on the same lines."""
+    b, o = chunk0
+    ref = sp.stream(chunk_lines=C, chunk_bytes=b.numel(), output=output, lag=lag)
+    ref.submit_packed(b, o)
+    bank = sp.protocols._bank
+    exp = per_line([r.detach() for r in ref.drain()], bank)
+    got = per_line(head, bank)[:C]
+    raw = b.numpy()
+    bad = sum(e != g for e, g in zip(exp, got)) + abs(len(exp) - len(got))
+    k, texts = 0, 0
+    for r in head:      # ChunkResult.line(i): the line's bytes, terminator included
+        for i in range(0, r.n, 997):
+            if k + i < C:
+                texts += r.line(i) != raw[o[k + i]: o[k + i + 1]].tobytes()
+        k += r.n
+    return {"lines": C, "mismatches": int(bad + texts), "against": "submit_packed"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--lines", type=int, default=1_000_000, help="corpus lines (streamed --passes times)")
@@ -53,6 +100,7 @@ def main():
     ap.add_argument("--lag", type=int, default=3)
     ap.add_argument("--output", default="wire", choices=("wire", "json"))
     ap.add_argument("--check", action="store_true")
+    ap.add_argument("--bytes", action="store_true", help="feed raw bytes through submit_bytes (lines split on the device)")
     ap.add_argument("--profile", action="store_true", help="cProfile the timed loop (top 30 by own time, stderr)")
     args = ap.parse_args()
     import torch
@@ -80,10 +128,27 @@ def main():
         b = torch.from_numpy(data[o[0]: o[-1]].copy()).pin_memory()
         chunks.append((b, o - o[0]))
     maxb = max(b.numel() for b, _ in chunks)
-    ls = sp.stream(chunk_lines=C, chunk_bytes=maxb, output=args.output, lag=args.lag)
+    if args.bytes:
+        # the pass as one byte string: the corpus lines carry the firmware's '\n' (synth.frame), so the
+        # string is their concatenation; pieces of equal size, so all but the last end mid-line.  A piece
+        # holds about C lines: room for a tenth more, and for the carried line start
+        o = offsets[: nck * C + 1].astype(np.int64)
+        raw_np = data[: o[-1]]
+        assert (raw_np[o[1:] - 1] == 10).all() and int(np.count_nonzero(raw_np == 10)) == nck * C, \
+            "every corpus line ends in its only newline"
+        raw = torch.from_numpy(raw_np.copy()).pin_memory()
+        step = -(-raw.numel() // nck)
+        feed = [raw[k * step: (k + 1) * step] for k in range(nck)]
+        assert all(p.is_pinned() for p in feed)    # uploaded from where they are, as the packed mode's chunks
+        ls = sp.stream(chunk_lines=C + C // 10 + 16, chunk_bytes=step + 65536, output=args.output, lag=args.lag)
+        submit = ls.submit_bytes
+    else:
+        feed = chunks
+        ls = sp.stream(chunk_lines=C, chunk_bytes=maxb, output=args.output, lag=args.lag)
+        submit = lambda ch: ls.submit_packed(*ch)   # noqa: E731
     # warm-up: one pass through every stage (kernels loaded, buffers touched)
-    for b, o in chunks[:2]:
-        ls.submit_packed(b, o)
+    for ch in feed:
+        submit(ch)
     ls.drain()
     ls.kernel_events.clear()
     ls.h2d_bytes = ls.d2h_bytes = 0
@@ -97,23 +162,28 @@ def main():
         prof = cProfile.Profile()
         prof.enable()
     t0 = time.perf_counter()
+    head = []     # --bytes --check: the results of the first chunks, until they cover C lines
     for k in range(nsteps):
-        b, o = chunks[k % nck]
         h0 = time.perf_counter()
-        ls.submit_packed(b, o)
+        submit(feed[k % nck])
         for r in ls.poll():
             if first is None and args.check:
                 first = r.detach()
+            if args.bytes and args.check and sum(x.n for x in head) < C:
+                head.append(r.detach())
         host_t += time.perf_counter() - h0
     for r in ls.drain():
         if first is None and args.check:
             first = r.detach()
+        if args.bytes and args.check and sum(x.n for x in head) < C:
+            head.append(r.detach())
     dt = time.perf_counter() - t0
+    nsteps = len(ls.kernel_events)     # the chunks queued (--bytes: the stream cuts them)
     if prof is not None:
         import pstats
         prof.disable()
         pstats.Stats(prof, stream=sys.stderr).sort_stats("tottime").print_stats(30)
-    total = nsteps * C
+    total = nck * C * args.passes
     ke = ls.kernel_events
     k_parse = float(np.median([a.elapsed_time(b) * 1e-3 for a, b, _, _ in ke]))
     k_demod = float(np.median([c.elapsed_time(d) * 1e-3 for _, _, c, d in ke]))
@@ -131,7 +201,7 @@ def main():
         "metric": "raw firmware lines/sec end to end: pinned host lines -> parse + demodulate + serialise -> results "
                   "in pinned host memory (PCIe both ways, overlapped; SignalParser.stream)",
         "value": total / dt, "unit": "lines/s", "n_gpus": 1, "lines": total, "chunk_lines": C, "lag": args.lag,
-        "output": args.output, "ms_per_chunk": 1e3 * per_chunk,
+        "output": args.output, "input": "bytes" if args.bytes else "packed", "chunks": nsteps, "ms_per_chunk": 1e3 * per_chunk,
         "kernels_ms_per_chunk": {"parse+select": 1e3 * k_parse, "demod+serialise": 1e3 * k_demod},
         "chunk_span_ms_median": 1e3 * float(np.median(span)),
         "host_ms_per_chunk": 1e3 * host_t / nsteps,
@@ -144,7 +214,12 @@ def main():
         "data": "synthetic firmware lines (synth.line_corpus: MU/MS/MC 1/3 each, 30 % of MU/MS Mred=1 compressed)",
     }
     res["bound"] = max(stages, key=stages.get)
-    if args.check:
+    if args.check and args.bytes:
+        res["check"] = check_bytes(sp, chunks[0], head, C, args.output, args.lag)
+        if res["check"]["mismatches"]:
+            print(json.dumps(res), flush=True)
+            raise SystemExit(f"--check: {res['check']['mismatches']} lines differ from the packed mode's")
+    elif args.check:
         b, o = chunks[0]
         b = b.numpy()
         lines = [b[o[i]: o[i + 1]].tobytes() for i in range(C)]
