@@ -23,6 +23,8 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 
 DEPS = [*SRCS, os.path.join(HERE, "csrc", "sdx_device.h"), os.path.join(HERE, "csrc", "sdx_lane.h"),
         os.path.join(HERE, "csrc", "sdx_mc.h"),
+        os.path.join(HERE, "csrc", "sdx_tile.h"),        # MU/MS tile engine (sdx_kernels.hip)
+        os.path.join(HERE, "csrc", "sdx_mc_blocks.h"),   # MC blocks (sdx_kernels.hip)
         os.path.join(HERE, "csrc", "sdx_strtod.h"),      # exact float(), host + device (sdx_lines.hip)
         os.path.join(HERE, "csrc", "sdx_dtoa.h"),        # repr(float), host + device (sdx_json.hip)
         os.path.join(HERE, "csrc", "sdx_dtoa_pow10.h"),  # its powers of ten (tools/gen_dtoa_pow10.py)

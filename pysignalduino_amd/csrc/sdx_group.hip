@@ -41,12 +41,6 @@ SDX_DEV uint64_t peers8(uint32_t v, bool active) {
 // the clock-grouped processing order.)
 // ---------------------------------------------------------------------------------------------
 constexpr int SIG_PROTOS = 32;
-#ifndef SDX_MS_LONG_FIRST
-#define SDX_MS_LONG_FIRST 0  // 1: the MS length class of more than 128 pulses first (A/B)
-#endif
-#ifndef SDX_MS_KEY
-#define SDX_MS_KEY 0  // MS key form (A/B experiments; 0 = ascending signature)
-#endif
 template <int KIND>
 SDX_DEV void sig_block(const void* __restrict__ bank, const sdx_pulse_batch& b, uint32_t* __restrict__ key,
                        uint32_t* __restrict__ msg_out, sdx_msg_rec* __restrict__ mrec, const int blk) {
@@ -162,22 +156,12 @@ SDX_DEV void sig_block(const void* __restrict__ bank, const sdx_pulse_batch& b, 
     // MU: descending signature order -- messages that pass the leading protocols, the tiles that
     // run the expensive search most, start first and the cheap tiles fill the kernel's tail
     // (MU 1.29 -> 1.21 ms; popcount-first keys measured 1.24 ms); MS measured better ascending
-#if SDX_MS_KEY == 1
-    const uint32_t ms_key = ~sig;
-#elif SDX_MS_KEY == 2  // survivor count descending, then signature
-    const uint32_t ms_key = ((uint32_t)(32 - popc64(sig)) << 26) | (sig >> 6);
-#elif SDX_MS_KEY == 3  // survivor count ascending, then signature
-    const uint32_t ms_key = ((uint32_t)popc64(sig) << 26) | (sig >> 6);
-#else
-    // (SDX_MS_NARROW: the top bit = the length class of sdx_demod_pulses' MS launches, more than 128
-    // pulses, so each class's tiles come together, the signature below it)
-    uint32_t ms_key = sig;
-    if (SDX_MS_NARROW) {
-      const int64_t o = b.offsets_dev[msg];
-      const int len = b.len_dev ? b.len_dev[msg] : (int)(b.offsets_dev[msg + 1] - o);
-      ms_key = (((len > 128) != (SDX_MS_LONG_FIRST != 0)) ? 0x80000000u : 0u) | (sig >> 1);
-    }
-#endif
+    // (the other MS key forms tried, descending and survivor count first, were dropped).
+    // MS: the top bit = the length class of the MS tiles (ms_tile_by_class), more than 128 pulses, so
+    // each class's tiles come together and the long class last; the signature below it
+    const int64_t o = b.offsets_dev[msg];
+    const int len = b.len_dev ? b.len_dev[msg] : (int)(b.offsets_dev[msg + 1] - o);
+    const uint32_t ms_key = (len > 128 ? 0x80000000u : 0u) | (sig >> 1);
     key[i] = KIND == SDX_KIND_MU ? ~sig : ms_key;
     msg_out[i] = (uint32_t)msg;
   }
@@ -211,15 +195,7 @@ __global__ __launch_bounds__(256) void k_sig2(const void* __restrict__ bank, Sig
 // totals).  No inter-workgroup waiting: a decoupled look-back sort is latency-bound at these sizes.
 // ---------------------------------------------------------------------------------------------
 constexpr int RS_T = 512, RS_ROUNDS = 4, RS_PART = RS_T * RS_ROUNDS;
-#ifndef SDX_RS_PASSES
-#define SDX_RS_PASSES 4
-#endif
-#ifndef SDX_RS_PASSES_MS
-#define SDX_RS_PASSES_MS SDX_RS_PASSES
-#endif
-constexpr int RS_PASSES = SDX_RS_PASSES;  // bytes of the key sorted on, from the top
-constexpr int RS_PASSES_MS = SDX_RS_PASSES_MS;  // (MS: A/B)
-static_assert(RS_PASSES >= 1 && RS_PASSES <= 4 && RS_PASSES_MS >= 1 && RS_PASSES_MS <= 4, "1..4 radix passes");
+constexpr int RS_PASSES = 4;  // bytes of the key sorted on, from the top
 
 // hist[digit * np + part] = elements of the partition with that digit in pass d
 SDX_DEV void rs_hist(const uint32_t* __restrict__ key, int n, int np, int d, uint32_t* __restrict__ hist, const int p,
@@ -381,12 +357,11 @@ bool group_messages(const void* bank_dev, int kind, const sdx_pulse_batch& b, in
     hipLaunchKernelGGL((k_sig<SDX_KIND_MS>), dim3(grid), dim3(256), 0, st, bank_dev, b, k0, v0, mrec);
   // the key's top RS_PASSES bytes (LSD order): (k0, v0) -> (k1, v1) -> (k0, v0) -> ..., the last
   // pass writing the message indices to order
-  const int passes = kind == SDX_KIND_MU ? RS_PASSES : RS_PASSES_MS;
-  for (int pi = 0; pi < passes; ++pi) {
-    const int d = 4 - passes + pi;
+  for (int pi = 0; pi < RS_PASSES; ++pi) {
+    const int d = 4 - RS_PASSES + pi;
     const bool even = (pi & 1) == 0;
     uint32_t* kin = even ? k0 : k1;
-    uint32_t* vout = pi == passes - 1 ? reinterpret_cast<uint32_t*>(order) : (even ? v1 : v0);
+    uint32_t* vout = pi == RS_PASSES - 1 ? reinterpret_cast<uint32_t*>(order) : (even ? v1 : v0);
     hipLaunchKernelGGL(k_rs_hist, dim3(np), dim3(RS_T), 0, st, kin, n, np, d, hist);
     hipLaunchKernelGGL(k_rs_scan_rows, dim3(256 / 4), dim3(256), 0, st, hist, np, tot);
     hipLaunchKernelGGL(k_rs_scatter, dim3(np), dim3(RS_T), 0, st, kin, even ? v0 : v1, n, np, d, hist, tot,
@@ -400,7 +375,6 @@ bool group_messages(const void* bank_dev, int kind, const sdx_pulse_batch& b, in
 bool group_messages2(const void* bank_dev, const sdx_pulse_batch& bmu, int32_t* omu, sdx_msg_rec* rmu, uint8_t* wmu,
                      size_t cmu, const sdx_pulse_batch& bms, int32_t* oms, sdx_msg_rec* rms, uint8_t* wms, size_t cms,
                      hipStream_t st) {
-  static_assert(RS_PASSES == RS_PASSES_MS, "one pass count for both sorts");
   const int nmu = bmu.sel_dev ? bmu.n_sel : bmu.n, nms = bms.sel_dev ? bms.n_sel : bms.n;
   if (nmu <= 0 || nms <= 0 || cmu < group_bytes(nmu) || cms < group_bytes(nms)) return false;
   struct Side {

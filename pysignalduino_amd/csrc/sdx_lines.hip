@@ -184,12 +184,7 @@ LD int find_semi(const Str& P, int s) {
 LD bool next_part(const Str& P, int& pos, int& s, int& e) {
   while (pos <= P.n) {
     s = pos;
-#ifdef SDX_NEXTPART_BYTES
-    e = s;
-    while (e < P.n && P.p[e] != ';') ++e;
-#else
     e = find_semi(P, s);
-#endif
     pos = e + 1;
     if (e > s) return true;
   }
@@ -613,10 +608,7 @@ LD uint64_t sw_hexalpha(uint64_t x) {  // 'a'..'f' / 'A'..'F'
 // (CLS_ANY: any ASCII byte).  P[0, n) must end with ';'.  The aligned 8-byte words are loaded
 // SCAN_W at a time (independent loads: one memory round trip per SCAN_W words of a long field
 // instead of one per word); a word holding no byte of [0, n) is not loaded.
-#ifndef SDX_SCAN_W
-#define SDX_SCAN_W 4
-#endif
-constexpr int SCAN_W = SDX_SCAN_W;
+constexpr int SCAN_W = 4;
 LD int scan_run(const uint8_t* P, int n, int s, int cls) {
   const uint8_t* q = P + s;
   const int a = (int)((uintptr_t)q & 7);
@@ -1194,7 +1186,6 @@ __global__ __launch_bounds__(PT) __attribute__((amdgpu_waves_per_eu(6))) void k_
   unsigned long long* lp = lpl - 10;
 #endif
   LP_T(tk0);
-#ifndef SDX_NO_LPREFETCH
   {  // The wave's 64 lines are contiguous in bytes_dev: read them once with coalesced 16-byte loads,
      // all in flight together, so that the lane-private byte loads below (strip, header, the fast
      // path's word scans) hit the caches instead of each lane starting its own chain of cold misses
@@ -1222,7 +1213,6 @@ __global__ __launch_bounds__(PT) __attribute__((amdgpu_waves_per_eu(6))) void k_
       asm volatile("" ::"v"(acc));  // keeps the loads
     }
   }
-#endif
   if (valid) {
     LP_T(tl0);
     const int64_t lo = in.offsets_dev[i], hi = in.offsets_dev[i + 1];
@@ -1355,11 +1345,6 @@ __global__ __launch_bounds__(PT) __attribute__((amdgpu_waves_per_eu(6))) void k_
 // beside.  Anything else (a second data part, a skeleton past its buffer, data longer than
 // SDX_LONG_MAX, a payload the fast path declines) is parsed from the slot as before.
 constexpr int SKEL = 136;  // skeleton bytes per lane (8 * 17: lanes spread over the LDS banks)
-#ifdef SDX_NO_SKEL
-constexpr bool kSkel = false;  // A/B: parse from the slot
-#else
-constexpr bool kSkel = true;
-#endif
 struct SkelWriter {
   Writer8 g;    // the slot
   LdsWriter k;  // the skeleton
@@ -1438,7 +1423,7 @@ LD void parse_compressed(const sdx_lines& in, const sdx_lines_out& out, int i, u
       const uint8_t ty = K.n > 1 ? K.p[1] : 0;
       LP_T(t2);
       bool fast = false;
-      if (kSkel && !w.k.ovf && w.nd == 1 && w.dlen <= SDX_LONG_MAX && (ty == 'U' || ty == 'S') && fast_payload(K.p, K.n, r, out, i)) {
+      if (!w.k.ovf && w.nd == 1 && w.dlen <= SDX_LONG_MAX && (ty == 'U' || ty == 'S') && fast_payload(K.p, K.n, r, out, i)) {
         fast = true;
         r.dE = r.dS + w.dlen;  // the data value's real extent (its position is the skeleton's)
         finish_fields(K, r, out, i);

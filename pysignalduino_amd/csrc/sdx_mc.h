@@ -1,5 +1,5 @@
 // sdx_mc.h -- the Manchester (MC) protocol methods on the device, shared by the "fixed" MC chain
-// (k_mc, sdx_kernels.hip) and the unit-level entry (k_units, sdx_units.hip).
+// (k_mc: sdx_mc_blocks.h, sdx_kernels.hip) and the unit-level entry (k_units, sdx_units.hip).
 //
 // A frame's bit string lives in LDS as MSB-first 64-bit words, lane-strided (word w of lane t at
 // base[w * 256], 256 threads per workgroup).  mc_method restates the reference's methods

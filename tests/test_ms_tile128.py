@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 TILES = (128, 64)
 ROUTES = ("pulses", "step")
-# the 128-message tile's pools (TileLds<2, 128, 2> in sdx_kernels.hip): staged records, payload bytes
+# the 128-message tile's pools (TileLds<2, 128, 2> in sdx_tile.h): staged records, payload bytes
 PREC_128, PHEAP_128 = 512, 16384
 
 
