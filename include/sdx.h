@@ -465,6 +465,31 @@ typedef struct {
 } sdx_json_out;
 
 int sdx_serialize_json(const sdx_bank* bank, const sdx_json_in* in, const sdx_json_out* out, void* hip_stream);
+/* sdx_serialize_json where a line with skip_dev[line] != 0 gets no text (len 0) and takes no space in
+ * json_dev (first_only = 0: every record of such a line).  skip_dev = NULL: sdx_serialize_json. */
+int sdx_serialize_json_skip(const sdx_bank* bank, const sdx_json_in* in, const sdx_json_out* out,
+                            const uint8_t* skip_dev, void* hip_stream);
+
+/* ---- repeat suppression --------------------------------------------------------
+ * A stick delivers every telegram several times, each repetition as its own line.  In line order
+ * within one stream of lines: a line is RESULT-BEARING when its descriptor in its kind's launch is
+ * SDX_ST_OK with n_rec > 0 (the lines sdx_serialize_json's first_only modes give a text); its KEY is
+ * (kind, proto, payload bytes) of its first record; it is a REPEAT when its key equals the key of the
+ * previous result-bearing line.  Lines without results neither start nor break a run.
+ * sdx_mark_repeats writes repeat_dev[line] = 1 for the repeats of a chunk of n lines and 0 for every
+ * other line.  kinds[0..k): what the chunk's sdx_serialize_json calls take, one per kind (k = 1..4, no
+ * kind twice); only kind, desc_dev, rec_dev, heap_dev and n (= the chunk's n) are read.  state_dev
+ * (sdx_repeat_state_bytes(), 16-byte aligned) carries the key and payload of the last result-bearing
+ * line from one chunk of a stream to the next: zero its first 16 bytes to start a stream; a chunk
+ * without a result-bearing line leaves it untouched.  key_scratch_dev: sdx_repeat_scratch_bytes(n)
+ * bytes, 16-byte aligned, contents free.  Four kernels on the caller's stream (keys and per-tile
+ * summary, tile scan, resolve, state); no allocation, no synchronisation, nothing read past a
+ * payload's end.  Pass repeat_dev as sdx_serialize_json_skip's skip_dev to leave the repeats out. */
+size_t sdx_repeat_state_bytes(void);
+size_t sdx_repeat_scratch_bytes(int32_t n);
+int sdx_repeat_tile(void);   /* lines per tile of the scan (SDX_REPEAT_TILE) */
+int sdx_mark_repeats(const sdx_bank* bank, const sdx_json_in* kinds, int k, int32_t n, uint8_t* repeat_dev,
+                     void* key_scratch_dev, void* state_dev, void* hip_stream);
 
 /* ---- unit-level entry ------------------------------------------------------------------------
  * The reference's helper methods that its own unit tests call on SDProtocols, evaluated on n

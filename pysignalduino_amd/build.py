@@ -12,6 +12,7 @@ SRCS = [os.path.join(HERE, "csrc", "sdx_kernels.hip"),   # demodulation kernels 
         os.path.join(HERE, "csrc", "sdx_split.hip"),     # byte-stream input (sdx_split_lines)
         os.path.join(HERE, "csrc", "sdx_mn.hip"),        # MN (FSK) engine (sdx_demod_mn)
         os.path.join(HERE, "csrc", "sdx_json.hip"),      # publish-ready JSON (sdx_serialize_json)
+        os.path.join(HERE, "csrc", "sdx_repeat.hip"),    # repeat suppression (sdx_mark_repeats)
         os.path.join(HERE, "csrc", "sdx_units.hip"),     # unit-level helpers (sdx_units)
         os.path.join(HERE, "csrc", "sdx_exchange.hip"),  # multi-GPU exchange packing (sdx_exchange_pack)
         os.path.join(HERE, "csrc", "sdx_group.hip"),     # MU/MS message grouping (k_sig + radix sort)
@@ -28,6 +29,7 @@ DEPS = [*SRCS, os.path.join(HERE, "csrc", "sdx_device.h"), os.path.join(HERE, "c
         os.path.join(HERE, "csrc", "sdx_strtod.h"),      # exact float(), host + device (sdx_lines.hip)
         os.path.join(HERE, "csrc", "sdx_dtoa.h"),        # repr(float), host + device (sdx_json.hip)
         os.path.join(HERE, "csrc", "sdx_dtoa_pow10.h"),  # its powers of ten (tools/gen_dtoa_pow10.py)
+        os.path.join(HERE, "csrc", "sdx_repeat_layout.h"),  # sdx_mark_repeats' buffer layout (sdx_repeat.hip)
         os.path.join(os.path.dirname(HERE), "include", "sdx.h"),
         os.path.join(os.path.dirname(HERE), "include", "sdx_bank.h")]
 

@@ -33,6 +33,12 @@ they have none: ``_handle_as_command_response(line)`` (controller.py:360-387) on
 command responses and logs at DEBUG, so it is awaited for a line only while the controller has
 pending responses or its logger is enabled for DEBUG (a controller without ``_pending_responses``
 gets it for every line); an unbounded ``asyncio.Queue`` is drained in bulk.
+
+``collapse_repeats=True`` drops consecutive equal telegrams (pysignalduino_amd/repeats.py: a line whose
+first decoded message has the kind, protocol and payload of the previous decoding line's): such a line
+causes no ``message_callback`` and no publication -- on the JSON path its text is never built -- while
+``_handle_as_command_response`` still gets every line.  The run of equal lines continues across
+micro-batches.
 """
 from __future__ import annotations
 
@@ -44,7 +50,8 @@ from typing import Any, Deque, Dict, List, Optional
 
 class BatchingParserTask:
     def __init__(self, controller: Any, max_batch: int = 4096, max_delay: float = 0.005, publish: str = "objects",
-                 logger: Optional[logging.Logger] = None, stream: bool = True, lag: int = 3):
+                 logger: Optional[logging.Logger] = None, stream: bool = True, lag: int = 3,
+                 collapse_repeats: bool = False):
         if publish not in ("objects", "json"):
             raise ValueError("publish must be 'objects' or 'json'")
         if publish == "json" and getattr(controller, "message_callback", None):
@@ -61,6 +68,8 @@ class BatchingParserTask:
         self.use_stream = stream and publish == "json"
         self.lag = lag
         self._stream = None
+        self.collapse = bool(collapse_repeats)
+        self._last_key = None     # publish='objects': the key of the last decoding line (repeats.objects_key)
 
     def install(self) -> "BatchingParserTask":
         """Replace the controller's per-line loop (the attribute its run() schedules)."""
@@ -202,7 +211,8 @@ class BatchingParserTask:
         lines the device hands back), never on the event loop."""
         c = self.c
         if self._stream is None:
-            self._stream = c.parser.stream(chunk_lines=self.max_batch, output="json", lag=self.lag)
+            kw = {"collapse_repeats": True} if self.collapse else {}
+            self._stream = c.parser.stream(chunk_lines=self.max_batch, output="json", lag=self.lag, **kw)
         ls = self._stream
         # chunk id -> its lines: results are matched to their lines by id, never by position, so a
         # publication that fails part-way through a chunk cannot shift later chunks onto the wrong lines
@@ -249,6 +259,29 @@ class BatchingParserTask:
             except Exception as e:  # noqa: BLE001
                 self.logger.error(f"Parser task error while draining {n} in-flight lines: {e}")
 
+    def _parse_collapsed(self, lines: List[Any]) -> List[Any]:
+        """One micro-batch with the repeats dropped, the run continuing from the previous batch: texts
+        through a LineStream drained per batch (its state carries the last key on the device), objects
+        through parse_lines with the last key kept here."""
+        p = self.c.parser
+        if self.publish == "json":
+            if self._stream is None:
+                self._stream = p.stream(chunk_lines=self.max_batch, output="json", lag=1, collapse_repeats=True)
+            self._stream.submit(lines)
+            return self._stream.drain()[0].texts()
+        from .repeats import objects_key
+        results = p.parse_lines(lines, collapse_repeats=True)
+        first = True
+        for i, res in enumerate(results):
+            k = objects_key(res)
+            if k is None:
+                continue
+            if first and k == self._last_key:   # the batch's first decoding line repeats the previous batch's last
+                results[i] = []
+            first = False
+            self._last_key = k
+        return results
+
     async def run(self) -> None:
         c = self.c
         if self.use_stream:
@@ -258,7 +291,8 @@ class BatchingParserTask:
                 batch = await self._next_batch()
                 lines = list(filter(None, batch))
                 if lines:
-                    parse = c.parser.parse_lines_json if self.publish == "json" else c.parser.parse_lines
+                    parse = (self._parse_collapsed if self.collapse else
+                             c.parser.parse_lines_json if self.publish == "json" else c.parser.parse_lines)
                     results = await asyncio.to_thread(parse, lines)
                     self.batches += 1
                     for line, res in zip(lines, results):

@@ -308,14 +308,25 @@ class SignalParser:
             raise out
         return out
 
-    def parse_lines(self, lines: Sequence[Union[str, bytes]]) -> List[Union[List[DecodedMessage], Exception]]:
+    def parse_lines(self, lines: Sequence[Union[str, bytes]],
+                    collapse_repeats: bool = False) -> List[Union[List[DecodedMessage], Exception]]:
         """Batch form of parse_line: one upload, one parse launch, one launch per demodulation
         variant, one read-back.  Returns one DecodedMessage list per line (or the ContractError
-        for a line outside the device contract)."""
+        for a line outside the device contract).  ``collapse_repeats``: a line that repeats the
+        previous result-bearing line's (kind, protocol, payload) gives [] (repeats.py; the mask is
+        left in ``last_repeat_mask``)."""
         if len(lines) == 0:
-            return []
+            return self._collapsed([], collapse_repeats)
         data, offsets, bad = pack_lines(lines)
-        return self._objects(lines, LineBatch(self.protocols._ensure(), data, offsets), offsets, bad, len(data))
+        return self._collapsed(self._objects(lines, LineBatch(self.protocols._ensure(), data, offsets), offsets, bad,
+                                             len(data)), collapse_repeats)
+
+    def _collapsed(self, out: list, collapse: bool) -> list:
+        """Object output: every payload is on the host already, so the repeats are marked there."""
+        if collapse:
+            from .repeats import collapse_objects
+            self.last_repeat_mask = collapse_objects(out)
+        return out
 
     def _objects(self, lines, lb: LineBatch, offsets: np.ndarray, bad: dict, nbytes: int):
         """parse_lines from the uploaded batch on: ``lines`` indexable (lines[i] = line i's text),
@@ -503,25 +514,32 @@ class SignalParser:
 
     # ------------------------------------------------------------------------------------------
     def stream(self, chunk_lines: int = 250_000, chunk_bytes: Optional[int] = None, output: str = "json",
-               lag: int = 3):
+               lag: int = 3, collapse_repeats: bool = False):
         """A pipelined LineStream over this parser (pysignalduino_amd/stream.py): chunks of raw lines
         in, the controller's JSON texts (or the wire form) out, the PCIe copies, parse, demodulation
         and serialisation of successive chunks overlapping; the same per-line results as
         parse_lines_json / parse_lines."""
         from .stream import LineStream
-        return LineStream(self, chunk_lines=chunk_lines, chunk_bytes=chunk_bytes, output=output, lag=lag)
+        return LineStream(self, chunk_lines=chunk_lines, chunk_bytes=chunk_bytes, output=output, lag=lag,
+                          collapse_repeats=collapse_repeats)
 
-    def parse_lines_json(self, lines: Sequence[Union[str, bytes]]) -> List[Union[Optional[str], Exception]]:
+    def parse_lines_json(self, lines: Sequence[Union[str, bytes]],
+                         collapse_repeats: bool = False) -> List[Union[Optional[str], Exception]]:
         """Per line, the MQTT message text the reference controller publishes for it:
         ``MqttPublisher._message_to_json(parse_line(line)[0])`` (signalduino/controller.py:254-257,
         mqtt.py:227-245), or None when the line decodes to nothing -- parse, demodulation and JSON
-        serialisation (sdx_serialize_json) all on the device; only the texts come back."""
+        serialisation (sdx_serialize_json) all on the device; only the texts come back.
+        ``collapse_repeats``: a line that repeats the previous result-bearing line's (kind, protocol,
+        payload) gives None -- marked on the device (sdx_mark_repeats) and never serialised; the mask
+        is left in ``last_repeat_mask``."""
         if len(lines) == 0:
+            if collapse_repeats:
+                self.last_repeat_mask = np.zeros(0, np.uint8)
             return []
         data, offsets, bad = pack_lines(lines)
-        return self._texts(lines, LineBatch(self.protocols._ensure(), data, offsets), bad, len(data))
+        return self._texts(lines, LineBatch(self.protocols._ensure(), data, offsets), bad, len(data), collapse_repeats)
 
-    def _texts(self, lines, lb: LineBatch, bad: dict, nbytes: int):
+    def _texts(self, lines, lb: LineBatch, bad: dict, nbytes: int, collapse: bool = False):
         """parse_lines_json from the uploaded batch on (``lines`` and ``nbytes`` as in _objects)."""
         n = len(lines)
         eng = self.protocols._ensure()
@@ -550,19 +568,68 @@ class SignalParser:
         elig = self.protocols.mn_eligibility(self.rfmode)
         texts: List[Any] = [None] * n
         host_rows: List[int] = []   # lines whose text is built from parse_lines' objects (general paths)
+
+        def demodulate(kind, launches, rec_cap, heap_cap):
+            work = eng.pulses_work_bytes(n) if kind in (runtime.KIND_MU, runtime.KIND_MS) else 0
+            out = eng.alloc_out(n, rec_cap, heap_cap, work)  # MU/MS: grouped order + spill room
+            for bd, sel, long_v in launches:
+                if not sel.numel():
+                    continue
+                if kind == runtime.KIND_MN:
+                    eng.launch_mn(bd, out, elig=elig, sel=sel)
+                elif kind == runtime.KIND_MC:
+                    eng.launch_mc(bd, out, sel=sel)
+                else:
+                    eng.launch_pulses(kind, bd, out, sel=sel, long_variant=long_v)
+            return out
+
+        def take_texts(jo, used):
+            lens = jo["len"][:n].cpu().numpy()
+            offs = jo["off"][:n].cpu().numpy()
+            blob = jo["json"][: int(used)].cpu().numpy().tobytes()
+            for i in np.nonzero(lens > 0)[0]:
+                texts[int(i)] = blob[int(offs[i]): int(offs[i]) + int(lens[i])].decode("ascii")
+
+        rep = np.zeros(n, np.uint8)   # the device's repeat mask (collapse)
+        if collapse:
+            # every kind's launch first (their outputs stay on the device), then ONE sdx_mark_repeats over
+            # them, then the serialiser with the mask: a repeat is never turned into text
+            kept = []
+            for kind, rec_cap, heap_cap, json_cap, launches in jobs:
+                for _attempt in range(4):
+                    out = demodulate(kind, launches, rec_cap, heap_cap)
+                    c1 = out["cursor"].cpu().numpy()
+                    if kind == runtime.KIND_MC and c1[2] == 2:   # frames of > 128 hex characters: host rows
+                        sel = launches[0][1]
+                        st = out["desc"][: 8 * n].view(-1, 8)[:, 6][sel.long()].cpu().numpy()
+                        host_rows.extend(int(i) for i in sel.cpu().numpy()[st == runtime.ST_OVF_TILE])
+                        break
+                    if not c1[2]:
+                        break
+                    rec_cap, heap_cap = 4 * rec_cap, 4 * heap_cap
+                else:
+                    raise RuntimeError("result capacity overflow persists")
+                kept.append((kind, out, json_cap))
+            if kept:
+                rep_dev, scratch = eng.alloc_repeat(n)
+                eng.mark_repeats([eng.json_in(kind, out, lo, n) for kind, out, _ in kept], n, rep_dev, scratch,
+                                 eng.alloc_repeat_state())
+                for kind, out, json_cap in kept:
+                    for _attempt in range(4):
+                        jo = eng.alloc_json(n, json_cap)
+                        eng.launch_json(kind, out, lo, n, jo, first_only=True, skip=rep_dev)
+                        c2 = jo["cursor"].cpu().numpy()
+                        if not c2[1]:
+                            break
+                        json_cap *= 4
+                    else:
+                        raise RuntimeError("JSON capacity overflow persists")
+                    take_texts(jo, c2[0])
+                rep = rep_dev[:n].cpu().numpy()
+            jobs = []
         for kind, rec_cap, heap_cap, json_cap, launches in jobs:
             for _attempt in range(4):
-                work = eng.pulses_work_bytes(n) if kind in (runtime.KIND_MU, runtime.KIND_MS) else 0
-                out = eng.alloc_out(n, rec_cap, heap_cap, work)  # MU/MS: grouped order + spill room
-                for bd, sel, long_v in launches:
-                    if not sel.numel():
-                        continue
-                    if kind == runtime.KIND_MN:
-                        eng.launch_mn(bd, out, elig=elig, sel=sel)
-                    elif kind == runtime.KIND_MC:
-                        eng.launch_mc(bd, out, sel=sel)
-                    else:
-                        eng.launch_pulses(kind, bd, out, sel=sel, long_variant=long_v)
+                out = demodulate(kind, launches, rec_cap, heap_cap)
                 jo = eng.alloc_json(n, json_cap)
                 eng.launch_json(kind, out, lo, n, jo, first_only=True)
                 c1 = out["cursor"].cpu().numpy()
@@ -578,11 +645,7 @@ class SignalParser:
                 rec_cap, heap_cap, json_cap = 4 * rec_cap, 4 * heap_cap, 4 * json_cap
             else:
                 raise RuntimeError("result / JSON capacity overflow persists")
-            lens = jo["len"][:n].cpu().numpy()
-            offs = jo["off"][:n].cpu().numpy()
-            blob = jo["json"][: int(c2[0])].cpu().numpy().tobytes()
-            for i in np.nonzero(lens > 0)[0]:
-                texts[int(i)] = blob[int(offs[i]): int(offs[i]) + int(lens[i])].decode("ascii")
+            take_texts(jo, c2[0])
         status = lb.status[:n].cpu().numpy()
         kinds = lb.kind[:n].cpu().numpy()
         # ... and the unsupported MU/MS lines with them: parse_lines resolves the ones whose P# values
@@ -590,8 +653,13 @@ class SignalParser:
         exact = (status == runtime.LS_UNSUPPORTED) & ((kinds == runtime.LINE_MU) | (kinds == runtime.LINE_MS))
         grows = [int(i) for i in np.nonzero((status == runtime.LS_GENERAL) | exact)[0] if int(i) not in bad] + host_rows
         resolved = set()
+        has_text = np.fromiter((x is not None for x in texts), bool, n) if collapse else None
+        host_keys = {}   # collapse: the host-resolved rows' keys (None: no result)
         if grows:  # general-path lines (rare): their objects through parse_lines, the text as _message_to_json
             for i, g in zip(grows, self.parse_lines([lines[i] for i in grows])):
+                if collapse:
+                    from .repeats import objects_key
+                    host_keys[i] = objects_key(g)
                 if exact[i]:
                     if isinstance(g, ContractError):
                         continue   # still unsupported: reported below, under its index in this batch
@@ -607,10 +675,26 @@ class SignalParser:
             elif int(status[i]) == runtime.LS_UNSUPPORTED and i not in resolved:
                 texts[i] = ContractError(f"line {i} is outside the device contract of the front end "
                                          f"(kind {_KIND_NAME.get(int(kinds[i]), '?')})")
+        if collapse:
+            from .repeats import RepeatTracker, text_key
+            fetched = {}
+
+            def fetch_key(i):   # a flagged line whose run head the host does not know: the batch API
+                fetched[i] = self.parse_lines_json([lines[i]])[0]
+                return text_key(_KIND_NAME[int(kinds[i])], fetched[i]) if isinstance(fetched[i], str) else None
+
+            mask = RepeatTracker().fix_chunk(rep, has_text, lambda i: text_key(_KIND_NAME[int(kinds[i])], texts[i]),
+                                             host_keys, fetch_key=fetch_key)
+            for i in sorted(set(np.nonzero(mask != rep)[0].tolist()) | set(host_keys)):
+                if mask[i]:
+                    texts[i] = None      # a host-resolved repeat, or a repeat of a host-resolved line
+                elif i not in host_keys and rep[i]:  # the device skipped it, but its predecessor was a host row
+                    texts[i] = fetched[i] if i in fetched else self.parse_lines_json([lines[i]])[0]
+            self.last_repeat_mask = mask
         return texts
 
     # -- byte-stream input ---------------------------------------------------------------------------
-    def parse_bytes(self, data, final: bool = True):
+    def parse_bytes(self, data, final: bool = True, collapse_repeats: bool = False):
         """parse_lines over a transport's raw read buffer (bytes-like): the bytes are uploaded and split
         into lines on the device (sdx_split_lines: every '\\n' ends a line, as StreamReader.readline(),
         signalduino/transport.py:113-123).  ``final=True``: bytes after the last '\\n' are the last line
@@ -619,12 +703,15 @@ class SignalParser:
         next buffer."""
         lines, lb, tail = self._split_bytes(data, final)
         out = self._objects(lines, lb, lines.offsets, {}, int(lines.offsets[-1])) if len(lines) else []
+        out = self._collapsed(out, collapse_repeats)
         return out if final else (out, tail)
 
-    def parse_bytes_json(self, data, final: bool = True):
+    def parse_bytes_json(self, data, final: bool = True, collapse_repeats: bool = False):
         """parse_lines_json over a raw read buffer (see parse_bytes; the same return forms)."""
         lines, lb, tail = self._split_bytes(data, final)
-        out = self._texts(lines, lb, {}, int(lines.offsets[-1])) if len(lines) else []
+        if collapse_repeats:
+            self.last_repeat_mask = np.zeros(0, np.uint8)
+        out = self._texts(lines, lb, {}, int(lines.offsets[-1]), collapse_repeats) if len(lines) else []
         return out if final else (out, tail)
 
     def _split_bytes(self, data, final: bool):

@@ -47,7 +47,8 @@ EXPORTED = ["sdx_abi_version", "sdx_last_error", "sdx_source_hash", "sdx_layout_
             "sdx_general_work_bytes", "sdx_demod_pulses_general", "sdx_mc_general_work_bytes", "sdx_demod_mc_general",
             "sdx_lines_general", "sdx_lines_exact", "sdx_parse_floats", "sdx_format_floats", "sdx_copy_async", "sdx_copy_async_kind", "sdx_copy_async_narrow",
             "sdx_fill_async", "sdx_demod_step", "sdx_group_step", "sdx_split_work_bytes", "sdx_split_lines",
-            "sdx_host_count_byte"]
+            "sdx_host_count_byte", "sdx_serialize_json_skip", "sdx_mark_repeats", "sdx_repeat_state_bytes",
+            "sdx_repeat_scratch_bytes", "sdx_repeat_tile"]
 GROUP_MIN = int(os.environ.get("SDX_GROUP_MIN", "4096"))   # SDX_GROUP_MIN (the env: A/B of the grouping)
 
 
@@ -234,6 +235,16 @@ def load_library(path: Optional[str] = None):
     lib.sdx_demod_mn.restype = c_int
     lib.sdx_serialize_json.argtypes = [c_void_p, POINTER(SdxJsonIn), POINTER(SdxJsonOut), c_void_p]
     lib.sdx_serialize_json.restype = c_int
+    lib.sdx_serialize_json_skip.argtypes = [c_void_p, POINTER(SdxJsonIn), POINTER(SdxJsonOut), c_void_p, c_void_p]
+    lib.sdx_serialize_json_skip.restype = c_int
+    lib.sdx_mark_repeats.argtypes = [c_void_p, POINTER(SdxJsonIn), c_int, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.sdx_mark_repeats.restype = c_int
+    lib.sdx_repeat_state_bytes.argtypes = []
+    lib.sdx_repeat_state_bytes.restype = c_size_t
+    lib.sdx_repeat_scratch_bytes.argtypes = [c_int32]
+    lib.sdx_repeat_scratch_bytes.restype = c_size_t
+    lib.sdx_repeat_tile.argtypes = []
+    lib.sdx_repeat_tile.restype = c_int
     lib.sdx_parse_lines.argtypes = [POINTER(SdxLines), POINTER(SdxLinesOut), c_void_p]
     lib.sdx_parse_lines.restype = c_int
     lib.sdx_select_lines.argtypes = [POINTER(SdxLinesOut), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
@@ -659,18 +670,61 @@ class Engine:
         _check(self.lib, self.lib.sdx_split_lines(_ptr(bytes_t), nbytes, 1 if final else 0, _ptr(offsets_t), cap,
                                                   _ptr(count_t), _ptr(scratch_t), st))
 
-    def launch_json(self, kind: int, demod_out, lines_out, n: int, jout, first_only: bool = True) -> None:
+    @staticmethod
+    def json_in(kind: int, demod_out, lines_out, n: int, first_only=True) -> SdxJsonIn:
+        """The sdx_json_in of one demodulation launch (launch_json and mark_repeats take it)."""
+        return SdxJsonIn(kind, int(first_only), _ptr(demod_out["desc"]), _ptr(demod_out["rec"]),
+                         _ptr(demod_out["cursor"]), _ptr(demod_out["heap"]), _ptr(lines_out["meta"]),
+                         _ptr(lines_out.get("pat_val")), _ptr(lines_out.get("cp_slot")), n,
+                         0 if first_only else demod_out["rec_cap"])
+
+    def launch_json(self, kind: int, demod_out, lines_out, n: int, jout, first_only: bool = True, skip=None) -> None:
         """sdx_serialize_json over a demodulation launch's device outputs (no host sync).  first_only:
         True / 1 one text per line, 2 the same sparse (only lines with a text are written: launches of
-        several kinds share one output), False / 0 one text per record."""
-        ji = SdxJsonIn(kind, int(first_only), _ptr(demod_out["desc"]), _ptr(demod_out["rec"]),
-                       _ptr(demod_out["cursor"]), _ptr(demod_out["heap"]), _ptr(lines_out["meta"]),
-                       _ptr(lines_out.get("pat_val")), _ptr(lines_out.get("cp_slot")), n,
-                       0 if first_only else demod_out["rec_cap"])
+        several kinds share one output), False / 0 one text per record.  ``skip``: a device uint8[n]
+        mask (mark_repeats' output): lines with a non-zero entry get no text (sdx_serialize_json_skip)."""
+        ji = self.json_in(kind, demod_out, lines_out, n, first_only)
         jo = SdxJsonOut(_ptr(jout["json"]), _ptr(jout["off"]), _ptr(jout["len"]), _ptr(jout["cursor"]),
                         jout["cap"], 0)
-        _check(self.lib, self.lib.sdx_serialize_json(self.handle, ctypes.byref(ji), ctypes.byref(jo),
-                                                     self.stream_ptr()))
+        if skip is None:
+            _check(self.lib, self.lib.sdx_serialize_json(self.handle, ctypes.byref(ji), ctypes.byref(jo),
+                                                         self.stream_ptr()))
+            return
+        if skip.numel() * skip.element_size() < n:
+            raise ValueError("launch_json: skip holds fewer than n bytes")
+        _check(self.lib, self.lib.sdx_serialize_json_skip(self.handle, ctypes.byref(ji), ctypes.byref(jo),
+                                                          _ptr(skip), self.stream_ptr()))
+
+    # -- repeat suppression (sdx_mark_repeats, DESIGN.md §4k) -------------------------------------
+    def repeat_tile(self) -> int:
+        return int(self.lib.sdx_repeat_tile())
+
+    def alloc_repeat_state(self):
+        """The carried state of one stream of lines, zeroed: no previous result-bearing line."""
+        t = self.torch
+        return t.zeros(int(self.lib.sdx_repeat_state_bytes()), dtype=t.uint8, device=self.dev)
+
+    def alloc_repeat(self, n: int):
+        """(repeat mask uint8[n], key scratch) for chunks of up to n lines."""
+        t = self.torch
+        return (t.zeros(max(n, 1), dtype=t.uint8, device=self.dev),
+                t.empty(int(self.lib.sdx_repeat_scratch_bytes(max(n, 1))), dtype=t.uint8, device=self.dev))
+
+    def mark_repeats(self, json_ins, n: int, repeat, scratch, state, stream=None) -> None:
+        """sdx_mark_repeats on ``stream`` (default: the current one; no host sync): repeat[:n] = 1 for the
+        lines that repeat the previous result-bearing line's (kind, proto, payload).  ``json_ins``: the
+        chunk's SdxJsonIn, one per kind (json_in); ``state``: alloc_repeat_state() of this stream of lines."""
+        n = int(n)
+        if not 1 <= len(json_ins) <= 4:
+            raise ValueError("mark_repeats: 1 to 4 kinds")
+        if (repeat.numel() * repeat.element_size() < n or
+                scratch.numel() * scratch.element_size() < int(self.lib.sdx_repeat_scratch_bytes(n)) or
+                state.numel() * state.element_size() < int(self.lib.sdx_repeat_state_bytes())):
+            raise ValueError("mark_repeats: a buffer is too small for n")
+        arr = (SdxJsonIn * len(json_ins))(*json_ins)
+        st = self.stream_ptr() if stream is None else c_void_p(stream.cuda_stream)
+        _check(self.lib, self.lib.sdx_mark_repeats(self.handle, arr, len(json_ins), n, _ptr(repeat), _ptr(scratch),
+                                                   _ptr(state), st))
 
     def alloc_json(self, items: int, cap: int):
         t, d = self.torch, self.dev

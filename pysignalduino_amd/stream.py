@@ -50,6 +50,7 @@ _KINDS = (("MU", runtime.KIND_MU, runtime.SEL_MU_SHORT, runtime.SEL_MU_LONG),
 _FUSE = os.environ.get("SDX_STREAM_FUSE", "1") != "0"
 _GROUP2 = os.environ.get("SDX_STREAM_GROUP2", "1") != "0"   # A/B: one sdx_group_step vs two groupings
 _MC_SEP = os.environ.get("SDX_STREAM_MC_SEP") == "1"   # A/B: MC's short class in its own launch
+_STATE_HEAD = 16 + 240   # bytes of the repeat state read back per chunk: its header + a payload of up to 240 bytes
 
 
 class _NlView:
@@ -161,6 +162,7 @@ class ChunkResult:
         self.json = self.off = self.len = None
         self.wire = self.layout = None
         self.host = {}            # line -> result of the batch API (fallback lines)
+        self.repeat = None        # collapse_repeats: uint8[n], 1 = the line repeats the previous result-bearing one
         self.affix = {}
         # the chunk's text, for line(i): the submitted sequence, or packed (data, offsets), or a
         # submit_bytes chunk's bytes (_ChunkBytes) + the device's offsets
@@ -188,7 +190,7 @@ class ChunkResult:
         self.slot = None
         if isinstance(self.src_data, _ChunkBytes):   # views of the slot's or the caller's pinned memory
             self.src_data, self.src_offsets = self.src_data.copy(), self.src_offsets.copy()
-        for f in ("kind", "status", "off", "len", "wire"):
+        for f in ("kind", "status", "off", "len", "wire", "repeat"):
             v = getattr(self, f)
             if isinstance(v, np.ndarray):
                 setattr(self, f, v.copy())
@@ -270,13 +272,16 @@ class _Slot:
             self.jcap = 600 * C + 65536
             self.jout = eng.alloc_json(C, self.jcap)
             self.h_sizes = t.zeros(2 + 4 * len(self.outs), dtype=t.int32).pin_memory()
-            self.h_out = t.empty(self.jcap + 10 * C + 64, dtype=t.uint8).pin_memory()
+            self.h_out = t.empty(self.jcap + 11 * C + 64, dtype=t.uint8).pin_memory()
         else:
             from . import dist as sdist
             self.ser = sdist.Exchange.sender(eng)
             self.h_sizes = t.zeros(runtime.XCHG_COUNTS * len(self.outs) + 4 * len(self.outs), dtype=t.int32).pin_memory()
             cap = sum(16 * C + 8 * o["rec_cap"] + o["heap_cap"] + 64 for o in self.outs.values())
-            self.h_out = t.empty(cap + 2 * C + 64, dtype=t.uint8).pin_memory()
+            self.h_out = t.empty(cap + 3 * C + 64, dtype=t.uint8).pin_memory()
+        if ls.collapse:   # the repeat mask, sdx_mark_repeats' scratch, and the state's head read back per chunk
+            self.rep, self.rep_scratch = eng.alloc_repeat(C)
+            self.h_state = t.zeros(_STATE_HEAD, dtype=t.uint8).pin_memory()
         self.reset()
 
     def reset(self):
@@ -301,9 +306,10 @@ class LineStream:
     order (never blocks on a chunk newer than ``lag`` submits); drain() -> all of them (blocks)."""
 
     def __init__(self, parser, chunk_lines: int = 250_000, chunk_bytes: Optional[int] = None, output: str = "json",
-                 lag: int = 3):
+                 lag: int = 3, collapse_repeats: bool = False):
         if output not in ("json", "wire"):
             raise ValueError("output must be 'json' or 'wire'")
+        self.collapse = bool(collapse_repeats)
         import torch
         self.torch = torch
         self.parser = parser
@@ -314,6 +320,13 @@ class LineStream:
         self.C = int(chunk_lines)
         self.B = int(chunk_bytes or 256 * self.C)
         self.lag = max(1, int(lag))
+        if self.collapse:
+            # repeat suppression: ONE state per stream, written by every chunk's state pass;
+            # rep_ev orders the next chunk's sdx_mark_repeats (on the other demodulation stream) behind it
+            from .repeats import RepeatTracker
+            self.rep_state = self.eng.alloc_repeat_state()
+            self.rep_ev = None
+            self.tracker = RepeatTracker()
         self.slots = [_Slot(self) for _ in range(self.lag + 1)]
         dev = self.eng.dev
         # the parse at the highest priority: the host waits for chunk k's class counts before it can
@@ -420,6 +433,8 @@ class LineStream:
         for s in list(self.inflight):      # stages B and C of any chunk whose previous stage is done
             while s.stage in (1, 2) and s.ev.query():
                 self._advance(s, s.stage + 1)
+            if self.collapse and s.stage == 1:
+                break     # the chunks' repeat passes are enqueued in submission order
         while self.inflight and self.inflight[0].stage == 3 and self.inflight[0].ev.query():
             self._advance(self.inflight[0], 4)     # results leave in submission order
         return self._pop_done()
@@ -440,6 +455,12 @@ class LineStream:
         if want >= 4:
             while self.inflight and self.inflight[0] is not s:   # results leave in submission order
                 self._advance(self.inflight[0], 4)
+        if self.collapse and want >= 2 and s.stage == 1:   # stage B in submission order (the carried state)
+            for o in list(self.inflight):
+                if o is s:
+                    break
+                if o.stage == 1:
+                    self._stage_b(o)
         while 0 < s.stage < want:      # _collect frees the slot (stage 0): nothing left to advance
             if s.stage == 1:
                 self._stage_b(s)
@@ -591,15 +612,25 @@ class LineStream:
                     else:
                         eng.launch_pulses(kd, pb, s.outs[name], sel=sels[long_], long_variant=True)
             s.cnt = cnt
+            lo = {"meta": lb.meta, "pat_val": lb.pat_val, "cp_slot": lb.cp_slot}
+            if self.collapse:
+                # only these small kernels wait for the previous chunk (its state pass, on the other
+                # demodulation stream); this chunk's demodulation above is already enqueued beside it
+                if self.rep_ev is not None:
+                    sd.wait_event(self.rep_ev)
+                eng.mark_repeats([eng.json_in(kd, s.outs[name], lo, n, 2) for name, kd, _, _ in _KINDS if name in s.outs],
+                                 n, s.rep, s.rep_scratch, self.rep_state, stream=sd)
+                runtime.copy_async(s.h_state, self.rep_state[:_STATE_HEAD], sd)
+                self.rep_ev = t.cuda.Event()
+                self.rep_ev.record(sd)
             if self.output == "json":
                 jo = s.jout
                 runtime.fill_async(jo["cursor"], sd)
                 runtime.fill_async(jo["len"][:n], sd)
-                lo = {"meta": lb.meta, "pat_val": lb.pat_val, "cp_slot": lb.cp_slot}
                 for name, kd, short, long_ in _KINDS:
                     o = s.outs.get(name)
                     if o is not None and (cnt[short] or (long_ is not None and cnt[long_])):
-                        eng.launch_json(kd, o, lo, n, jo, first_only=2)
+                        eng.launch_json(kd, o, lo, n, jo, first_only=2, **({"skip": s.rep} if self.collapse else {}))
                 runtime.copy_async(s.h_sizes[:2], jo["cursor"], sd)
                 runtime.copy_async(s.h_sizes[2:], s.cursors.reshape(-1), sd)
             else:
@@ -653,6 +684,9 @@ class LineStream:
             runtime.copy_async(ho[b: b + n], lb.kind[:n], self.cout)
             runtime.copy_async(ho[b + n: b + 2 * n], lb.status[:n], self.cout)
             s.kb = b
+            if self.collapse:
+                runtime.copy_async(ho[b + 2 * n: b + 3 * n], s.rep[:n], self.cout)
+                self.d2h_bytes += n + _STATE_HEAD
             if s.src is not None:   # a submit_bytes chunk: the offsets the device found, for line(i)
                 runtime.copy_async(s.h_offs[: n + 1], lb.offsets[: n + 1], self.cout)
                 self.d2h_bytes += 8 * (n + 1)
@@ -705,10 +739,79 @@ class LineStream:
             res = (self.parser.parse_lines_json(lines) if self.output == "json" else self.parser.parse_lines(lines))
             for i, x in zip(rows, res):
                 r.host[i] = s.bad[i] if i in s.bad else x
+        if self.collapse:
+            self._fix_repeats(s, r, ho[b + 2 * n: b + 3 * n], redo_kinds, kname)
         self.done.append(r)
         self.inflight.remove(s)
         s.reset()
         s.stage = 0
+
+    def _fix_repeats(self, s: _Slot, r: ChunkResult, rep: np.ndarray, redo_kinds, kname) -> None:
+        """r.repeat = the chunk's exact mask: the device's, re-decided around the host-resolved rows
+        (repeats.RepeatTracker); texts and host results follow it."""
+        from .repeats import objects_key, text_key
+        n, kind, js = r.n, r.kind, self.output == "json"
+        name_of = lambda i: kname.get(int(kind[i]), "?")   # noqa: E731
+        host_keys = {i: ((text_key(name_of(i), x) if isinstance(x, str) else None) if js else objects_key(x))
+                     for i, x in r.host.items()}
+        redo = [i for i in r.host if redo_kinds and kname.get(int(kind[i])) in redo_kinds
+                and r.status[i] == runtime.LS_OK]
+        fetched = {}
+
+        def fetch(i):
+            fetched[i] = self.parser.parse_lines_json([self._line(s, i)])[0]
+            return text_key(name_of(i), fetched[i]) if isinstance(fetched[i], str) else None
+
+        if js:
+            has_key = r.len > 0
+            blob = r.json
+
+            def dev_key_of(i):
+                o = int(r.off[i])
+                return text_key(name_of(i), bytes(blob[o: o + int(r.len[i])]).decode("ascii"))
+        else:
+            has_key, dev_key_of = self._wire_keys(r)
+        # what the device's state held after this chunk (read back behind its state pass)
+        hs = s.h_state.numpy()
+        valid, kd, proto, ln = (int(x) for x in hs[:16].view(np.uint32))
+        end_key = None
+        if valid and ln <= _STATE_HEAD - 16:
+            pids = (self.bank.mu_pids, self.bank.ms_pids, self.bank.mc_pids, self.bank.mn_pids)[kd]
+            end_key = (("MU", "MS", "MC", "MN")[kd], str(pids[proto]), hs[16: 16 + ln].tobytes().decode("latin-1"))
+        mask = self.tracker.fix_chunk(rep, has_key, dev_key_of, host_keys, redo, fetch, end_key)
+        r.repeat = mask
+        if not js:
+            return
+        for i in sorted(set(np.nonzero(mask != rep)[0].tolist()) | set(host_keys)):
+            if mask[i]:
+                if i in r.host:
+                    r.host[i] = None
+                else:
+                    r.len[i] = 0           # a repeat of a host-resolved line: its text is not published
+            elif i not in host_keys and rep[i]:   # skipped on the device, but its predecessor was a host row
+                r.host[i] = fetched[i] if i in fetched else self.parser.parse_lines_json([self._line(s, i)])[0]
+
+    def _wire_keys(self, r: ChunkResult):
+        """wire output: (which lines have results, line -> key) from the chunk's wire sections; the
+        sections of a kind are decoded when a key of that kind is first asked for."""
+        names = list(r.names)
+        tabs = {"MU": self.bank.mu_pids, "MS": self.bank.ms_pids, "MC": self.bank.mc_pids, "MN": self.bank.mn_pids}
+        line_kind = {"MU": runtime.LINE_MU, "MS": runtime.LINE_MS, "MC": runtime.LINE_MC, "MN": runtime.LINE_MN}
+        has = np.zeros(r.n, bool)
+        for j, name in enumerate(names):
+            msg = r.sections(j)[0]
+            has |= ((msg & 0xFFFF) > 0) & (((msg >> 16) & 0xFF) == runtime.ST_OK) & (r.kind == line_kind[name])
+        cache = {}
+
+        def key_of(i):
+            name = {v: k for k, v in line_kind.items()}[int(r.kind[i])]
+            if name not in cache:
+                cache[name] = r.decode(names.index(name))
+            desc, rec, heap = cache[name]
+            x = rec[int(desc["rec_begin"][i])]
+            o = int(x["payload_off"])
+            return (name, str(tabs[name][int(x["proto"])]), heap[o: o + int(x["payload_len"])].tobytes().decode("latin-1"))
+        return has, key_of
 
     @staticmethod
     def _line(s: _Slot, i: int):

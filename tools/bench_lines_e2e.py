@@ -102,6 +102,9 @@ def main():
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--bytes", action="store_true", help="feed raw bytes through submit_bytes (lines split on the device)")
     ap.add_argument("--profile", action="store_true", help="cProfile the timed loop (top 30 by own time, stderr)")
+    ap.add_argument("--repeat", type=int, default=1, help="emit each synthetic line R times consecutively (as a stick "
+                    "delivers telegrams): --lines / R distinct lines, --lines lines in all")
+    ap.add_argument("--collapse", action="store_true", help="stream with collapse_repeats=True (repeats are never serialised)")
     args = ap.parse_args()
     import torch
     from pysignalduino_amd import frontend, runtime, synth
@@ -118,6 +121,14 @@ def main():
         data, offsets, bad = frontend.pack_lines(lines)
         assert not bad
         np.savez(cache, data=data, offsets=offsets)
+    if args.repeat > 1:   # the first lines / R corpus lines, each R times in a row (one gather, no Python loop)
+        R, m = args.repeat, (len(offsets) - 1) // args.repeat
+        idx = np.repeat(np.arange(m), R)
+        lens = np.diff(offsets)[idx]
+        new_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        src = np.repeat(offsets[:-1][idx] - new_off[:-1], lens) + np.arange(int(new_off[-1]))
+        data, offsets = data[src], new_off
+    ckw = {"collapse_repeats": True} if args.collapse else {}
     C = args.chunk
     nck = (len(offsets) - 1) // C
     assert nck >= 2, "need at least two chunks"
@@ -140,11 +151,12 @@ def main():
         step = -(-raw.numel() // nck)
         feed = [raw[k * step: (k + 1) * step] for k in range(nck)]
         assert all(p.is_pinned() for p in feed)    # uploaded from where they are, as the packed mode's chunks
-        ls = sp.stream(chunk_lines=C + C // 10 + 16, chunk_bytes=step + 65536, output=args.output, lag=args.lag)
+        ls = sp.stream(chunk_lines=C + C // 10 + 16, chunk_bytes=step + 65536, output=args.output, lag=args.lag,
+                       **ckw)
         submit = ls.submit_bytes
     else:
         feed = chunks
-        ls = sp.stream(chunk_lines=C, chunk_bytes=maxb, output=args.output, lag=args.lag)
+        ls = sp.stream(chunk_lines=C, chunk_bytes=maxb, output=args.output, lag=args.lag, **ckw)
         submit = lambda ch: ls.submit_packed(*ch)   # noqa: E731
     # warm-up: one pass through every stage (kernels loaded, buffers touched)
     for ch in feed:
@@ -201,6 +213,7 @@ def main():
         "metric": "raw firmware lines/sec end to end: pinned host lines -> parse + demodulate + serialise -> results "
                   "in pinned host memory (PCIe both ways, overlapped; SignalParser.stream)",
         "value": total / dt, "unit": "lines/s", "n_gpus": 1, "lines": total, "chunk_lines": C, "lag": args.lag,
+        "repeat": args.repeat, "collapse": bool(args.collapse),
         "output": args.output, "input": "bytes" if args.bytes else "packed", "chunks": nsteps, "ms_per_chunk": 1e3 * per_chunk,
         "kernels_ms_per_chunk": {"parse+select": 1e3 * k_parse, "demod+serialise": 1e3 * k_demod},
         "chunk_span_ms_median": 1e3 * float(np.median(span)),
