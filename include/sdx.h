@@ -491,6 +491,28 @@ int sdx_repeat_tile(void);   /* lines per tile of the scan (SDX_REPEAT_TILE) */
 int sdx_mark_repeats(const sdx_bank* bank, const sdx_json_in* kinds, int k, int32_t n, uint8_t* repeat_dev,
                      void* key_scratch_dev, void* state_dev, void* hip_stream);
 
+/* sdx_mark_repeats with a time window, as FHEM's dispatch ("Dropped due to short time or equal msg").
+ * times_dev[line]: the line's arrival time in microseconds (int64), non-decreasing over the stream's
+ * lines; window_us = W >= 0.  The stream carries (K, T): K the key of the previous result-bearing line,
+ * T the time of the last result-bearing line that was NOT marked.  A result-bearing line with key k and
+ * time t is a repeat when K exists, k == K and t - T <= W; otherwise it is published and T = t; K = k
+ * in both cases.  Lines without results neither start nor break a run and their times are not read.
+ * The anchor is the last PUBLISHED line: with times 0 s, 1.5 s, 2.5 s of one key and W = 2 s the third
+ * line is published.  state_dev: sdx_repeat_timed_state_bytes() bytes, 16-byte aligned, a layout of its
+ * own (header, T, payload: csrc/sdx_repeat_layout.h); zero its header to start a stream; after a chunk it
+ * holds the key of the chunk's last result-bearing line and the time of its last published one (T stays
+ * when the chunk published nothing, everything stays when it had no result).  scratch_dev:
+ * sdx_repeat_timed_scratch_bytes(n) bytes, 16-byte aligned, contents free.  Eight kernels on the
+ * caller's stream; no allocation, no synchronisation, no spinning.  PRECONDITION: the times do not
+ * decrease.  On input that violates it the mask is unspecified, but every kernel stays inside its
+ * buffers and ends: searches and walks are bounded by indices.  SDX_EINVAL (nothing launched): a null
+ * buffer, window_us < 0, a misaligned scratch_dev / state_dev / times_dev (8 bytes), bad kinds. */
+size_t sdx_repeat_timed_state_bytes(void);
+size_t sdx_repeat_timed_scratch_bytes(int32_t n);
+int sdx_mark_repeats_timed(const sdx_bank* bank, const sdx_json_in* kinds, int k, int32_t n,
+                           const int64_t* times_dev, int64_t window_us, uint8_t* repeat_dev, void* scratch_dev,
+                           void* state_dev, void* hip_stream);
+
 /* ---- unit-level entry ------------------------------------------------------------------------
  * The reference's helper methods that its own unit tests call on SDProtocols, evaluated on n
  * independent inputs in one launch (lane = item), with the device code the demodulation kernels

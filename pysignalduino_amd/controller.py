@@ -38,20 +38,25 @@ gets it for every line); an unbounded ``asyncio.Queue`` is drained in bulk.
 first decoded message has the kind, protocol and payload of the previous decoding line's): such a line
 causes no ``message_callback`` and no publication -- on the JSON path its text is never built -- while
 ``_handle_as_command_response`` still gets every line.  The run of equal lines continues across
-micro-batches.
+micro-batches.  ``repeat_window=SECONDS`` (with ``collapse_repeats``) also ends a run once its last
+published telegram is more than the window old, as FHEM dispatches (repeats.py): every line is stamped
+with ``time.monotonic_ns() // 1000`` when it is taken from ``_raw_message_queue`` (``clock``: another
+source of microseconds, for tests), and the stamps travel with the lines to the parser.
 """
 from __future__ import annotations
 
 import asyncio
 import collections
 import logging
-from typing import Any, Deque, Dict, List, Optional
+import time
+from typing import Any, Callable, Deque, Dict, List, Optional
 
 
 class BatchingParserTask:
     def __init__(self, controller: Any, max_batch: int = 4096, max_delay: float = 0.005, publish: str = "objects",
                  logger: Optional[logging.Logger] = None, stream: bool = True, lag: int = 3,
-                 collapse_repeats: bool = False):
+                 collapse_repeats: bool = False, repeat_window: Optional[float] = None,
+                 clock: Optional[Callable[[], int]] = None):
         if publish not in ("objects", "json"):
             raise ValueError("publish must be 'objects' or 'json'")
         if publish == "json" and getattr(controller, "message_callback", None):
@@ -70,6 +75,13 @@ class BatchingParserTask:
         self._stream = None
         self.collapse = bool(collapse_repeats)
         self._last_key = None     # publish='objects': the key of the last decoding line (repeats.objects_key)
+        from .repeats import window_to_us
+        self.window_us = window_to_us(repeat_window)
+        if self.window_us is not None and not self.collapse:
+            raise ValueError("repeat_window needs collapse_repeats=True")
+        self.clock = clock or (lambda: time.monotonic_ns() // 1000)
+        self._stamps: List[int] = []          # repeat_window: the arrival times of _next_batch's lines
+        self._carry = [None, 0, None]         # repeat_window, publish='objects': K, T, the last line's time
 
     def install(self) -> "BatchingParserTask":
         """Replace the controller's per-line loop (the attribute its run() schedules)."""
@@ -105,6 +117,7 @@ class BatchingParserTask:
         """Up to max_batch lines, waiting at most max_delay after the first; with ``first_timeout``
         [] when no line arrives within it."""
         q: asyncio.Queue = self.c._raw_message_queue
+        timed = self.window_us is not None
         if first_timeout is None:
             batch = [await q.get()]
         else:
@@ -112,11 +125,15 @@ class BatchingParserTask:
                 batch = [await asyncio.wait_for(q.get(), first_timeout)]
             except asyncio.TimeoutError:
                 return []
+        if timed:
+            self._stamps = [self.clock()]
         loop = asyncio.get_running_loop()
         deadline = loop.time() + self.max_delay
         while len(batch) < self.max_batch:
             n0 = len(batch)
             self._take(q, batch)
+            if timed and len(batch) > len(self._stamps):   # taken together: one reading of the clock
+                self._stamps += [self.clock()] * (len(batch) - len(self._stamps))
             if len(batch) > n0:
                 continue
             remaining = deadline - loop.time()
@@ -126,7 +143,15 @@ class BatchingParserTask:
                 batch.append(await asyncio.wait_for(q.get(), remaining))
             except asyncio.TimeoutError:
                 break
+            if timed:
+                self._stamps.append(self.clock())
         return batch
+
+    def _times_of(self, batch: List[Any]) -> Optional[List[int]]:
+        """The stamps of the batch's non-empty lines (None without a window)."""
+        if self.window_us is None:
+            return None
+        return [t for ln, t in zip(batch, self._stamps) if ln]
 
     async def _publish_json(self, text: str) -> None:
         pub = self.c.mqtt_publisher
@@ -212,6 +237,8 @@ class BatchingParserTask:
         c = self.c
         if self._stream is None:
             kw = {"collapse_repeats": True} if self.collapse else {}
+            if self.window_us is not None:
+                kw["repeat_window"] = self.window_us / 1e6
             self._stream = c.parser.stream(chunk_lines=self.max_batch, output="json", lag=self.lag, **kw)
         ls = self._stream
         # chunk id -> its lines: results are matched to their lines by id, never by position, so a
@@ -236,7 +263,8 @@ class BatchingParserTask:
                 batch = await self._next_batch(self.max_delay if pending else None)
                 lines = list(filter(None, batch))
                 if lines:
-                    pending[await asyncio.to_thread(ls.submit, lines)] = lines
+                    times = self._times_of(batch)
+                    pending[await asyncio.to_thread(ls.submit, lines, **({} if times is None else {"times": times}))] = lines
                     self.batches += 1
                     done = await asyncio.to_thread(ls.poll)
                 elif pending:           # the queue ran dry: publish everything in flight
@@ -259,16 +287,23 @@ class BatchingParserTask:
             except Exception as e:  # noqa: BLE001
                 self.logger.error(f"Parser task error while draining {n} in-flight lines: {e}")
 
-    def _parse_collapsed(self, lines: List[Any]) -> List[Any]:
+    def _parse_collapsed(self, lines: List[Any], times: Optional[List[int]] = None) -> List[Any]:
         """One micro-batch with the repeats dropped, the run continuing from the previous batch: texts
         through a LineStream drained per batch (its state carries the last key on the device), objects
-        through parse_lines with the last key kept here."""
+        through parse_lines with the last key kept here.  ``times`` (repeat_window): the lines' stamps;
+        the objects are then marked here, from the carried (K, T) on (repeats.collapse_objects)."""
         p = self.c.parser
         if self.publish == "json":
             if self._stream is None:
-                self._stream = p.stream(chunk_lines=self.max_batch, output="json", lag=1, collapse_repeats=True)
-            self._stream.submit(lines)
+                kw = {} if times is None else {"repeat_window": self.window_us / 1e6}
+                self._stream = p.stream(chunk_lines=self.max_batch, output="json", lag=1, collapse_repeats=True, **kw)
+            self._stream.submit(lines, **({} if times is None else {"times": times}))
             return self._stream.drain()[0].texts()
+        if times is not None:
+            from .repeats import collapse_objects
+            results = p.parse_lines(lines)
+            collapse_objects(results, times, self.window_us, self._carry)
+            return results
         from .repeats import objects_key
         results = p.parse_lines(lines, collapse_repeats=True)
         first = True
@@ -293,7 +328,8 @@ class BatchingParserTask:
                 if lines:
                     parse = (self._parse_collapsed if self.collapse else
                              c.parser.parse_lines_json if self.publish == "json" else c.parser.parse_lines)
-                    results = await asyncio.to_thread(parse, lines)
+                    times = self._times_of(batch)
+                    results = await asyncio.to_thread(parse, lines, *([] if times is None else [times]))
                     self.batches += 1
                     for line, res in zip(lines, results):
                         if isinstance(res, Exception):  # parse_line raised for this line

@@ -14,6 +14,8 @@
 //                  table or the carried state; kind / proto / length, then the payload bytes
 //   k_rep_state    one workgroup: key + payload of the chunk's last result-bearing line -> state
 // Payload bytes are read one at a time, [off, off + len) only: nothing past a payload's end.
+// sdx_mark_repeats_timed (a run also ends when its last published line is too old) follows below, with
+// kernels of its own behind k_rep_keys and k_rep_tiles.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -168,7 +170,336 @@ __global__ __launch_bounds__(T) void k_rep_state(Kinds in, const sdx_repeat_key*
   for (uint32_t i = threadIdx.x; i < v.z; i += T) dst[i] = src[i];
 }
 
+// ---- sdx_mark_repeats_timed: a run also ends when its anchor is more than W old -----
+// A stream carries (K, T): K the key of the previous result-bearing line, T the time of the last one that
+// was not marked.  A line is a repeat when its key equals K and t - T <= W; otherwise it is published and
+// T = t.  T is the last PUBLISHED line's time, so a decision depends on the decisions before it:
+//   segment head  a result-bearing line whose key differs from its predecessor's, or whose gap to it
+//                 exceeds W: T is never later than the predecessor's time, so it is published whatever
+//                 came before.  Found per line, as eq above.  The chunk's first result-bearing line is
+//                 always a head; the carried (K, T) decides whether it is published (SDX_RT_SREP: not).
+//   segment       a head and the lines behind it up to the next head: equal keys, every gap <= W
+//   orbit         inside a segment the published lines are head, succ(head), succ(succ(head)), ... with
+//                 succ(a) = the segment's first line behind a with t > t(a) + W
+// Eight launches, the first two those of sdx_mark_repeats:
+//   k_rep_keys, k_rep_tiles    keys, the last result-bearing line in front of every tile
+//   k_rept_heads   lane = line: predecessor as k_rep_resolve, key compare and gap -> flags, te (a line
+//                  without results takes its predecessor's time, so te is non-decreasing and a search
+//                  never stops on such a line), the tile's last head
+//   k_rep_tiles    over the tiles' last heads -> the last head in front of every tile
+//   k_rept_seg     lane = line: the line's segment head
+//   k_rept_succ    lane = line: succ by binary search, inside the wave over the lanes' registers
+//                  (shuffles), behind it galloping over te / seg in memory; then pointer doubling over
+//                  the tile (LDS, 8 rounds): the orbit's last line inside the tile and its first behind it
+//   k_rept_chain   one workgroup, thread = tile: an orbit that leaves its head's tile is followed from
+//                  tile to tile (one load per tile it enters; orbits of different segments in parallel)
+//                  and entered into the tiles it lands in; then the state: K as k_rep_state, T = the
+//                  time of the last line of the last head's orbit
+//   k_rept_mark    lane = line: the tile's heads and its entry walk their orbit inside the tile (LDS)
+// Every search and walk is bounded by indices: on times that decrease the mask is unspecified, but
+// nothing leaves its buffer and every loop ends.
+namespace sdxt {
+using sdxr::Kinds;
+using sdxr::last_bit;
+using sdxr::same_bytes;
+using sdxr::ST;
+using sdxr::T;
+using sdxr::WAVES;
+
+// t - anchor > w for anchor <= t (the precondition), whatever the two values: no signed overflow
+__device__ __forceinline__ bool past(int64_t t, int64_t anchor, int64_t w) {
+  return (uint64_t)t - (uint64_t)anchor > (uint64_t)w;
+}
+
+__global__ __launch_bounds__(T) void k_rept_heads(Kinds in, int n, const sdx_repeat_key* __restrict__ keys,
+                                                  const int32_t* __restrict__ tile_prev,
+                                                  const int64_t* __restrict__ times, int64_t window,
+                                                  const uint8_t* __restrict__ state, int64_t* __restrict__ te,
+                                                  uint8_t* __restrict__ flags, int32_t* __restrict__ tile_head,
+                                                  int32_t* __restrict__ tile_arr) {
+  __shared__ int32_t wlast[WAVES];
+  __shared__ int32_t whead[WAVES];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = blockIdx.x * T + threadIdx.x;
+  sdx_repeat_key key{SDX_REPEAT_NONE, 0, 0, 0};
+  if (g < n) {
+    const uint4 v = *reinterpret_cast<const uint4*>(keys + g);
+    key = sdx_repeat_key{v.x, v.y, v.z, v.w};
+  }
+  const bool have = key.kind != SDX_REPEAT_NONE;
+  const uint64_t m = __ballot(have);
+  if (lane == 0) wlast[wave] = m ? (int)(g + last_bit(m)) : -1;
+  __syncthreads();
+  uint32_t f = 0;
+  if (g < n) {
+    const uint64_t lower = lane ? m & (~0ull >> (64 - lane)) : 0ull;
+    int pred = -1;
+    if (lower) {
+      pred = g - lane + last_bit(lower);
+    } else {
+      for (int w = wave - 1; w >= 0 && pred < 0; --w) pred = wlast[w];
+      if (pred < 0) pred = tile_prev[blockIdx.x];
+    }
+    int64_t t = 0;
+    if (have) {
+      t = times[g];
+      f = SDX_RT_RB;
+      const uint8_t* mine = in.k[key.kind].heap + key.off;
+      if (pred >= 0) {
+        const uint4 v = *reinterpret_cast<const uint4*>(keys + pred);
+        const bool cont = !past(t, times[pred], window) && v.x == key.kind && v.y == key.proto && v.z == key.len &&
+                          same_bytes(mine, in.k[key.kind].heap + v.w, key.len);
+        if (!cont) f |= SDX_RT_HEAD;
+      } else {  // the chunk's first result-bearing line: the carried (K, T)
+        const sdx_repeat_timed_state_hdr h = *reinterpret_cast<const sdx_repeat_timed_state_hdr*>(state);
+        f |= SDX_RT_HEAD;
+        if (h.valid && !past(t, h.t, window) && h.kind == key.kind && h.proto == key.proto && h.len == key.len &&
+            same_bytes(mine, state + sizeof(sdx_repeat_timed_state_hdr), key.len))
+          f |= SDX_RT_SREP;
+      }
+    } else if (pred >= 0) {
+      t = times[pred];
+    }
+    te[g] = t;
+    flags[g] = (uint8_t)f;
+  }
+  const uint64_t hm = __ballot((f & SDX_RT_HEAD) != 0);
+  if (lane == 0) whead[wave] = hm ? (int)(g + last_bit(hm)) : -1;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int last = -1;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) last = max(last, whead[w]);
+    tile_head[blockIdx.x] = last;
+    tile_arr[blockIdx.x] = -1;
+  }
+}
+
+__global__ __launch_bounds__(T) void k_rept_seg(int n, const uint8_t* __restrict__ flags,
+                                                const int32_t* __restrict__ tile_prevhead, int32_t* __restrict__ seg) {
+  __shared__ int32_t whead[WAVES];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = blockIdx.x * T + threadIdx.x;
+  const bool head = g < n && (flags[g] & SDX_RT_HEAD);
+  const uint64_t hm = __ballot(head);
+  if (lane == 0) whead[wave] = hm ? (int)(g + last_bit(hm)) : -1;
+  __syncthreads();
+  if (g >= n) return;
+  const uint64_t upto = hm & (~0ull >> (63 - lane));
+  int s = -1;
+  if (upto) {
+    s = g - lane + last_bit(upto);
+  } else {
+    for (int w = wave - 1; w >= 0 && s < 0; --w) s = whead[w];
+    if (s < 0) s = tile_prevhead[blockIdx.x];
+  }
+  seg[g] = s;
+}
+
+__global__ __launch_bounds__(T) void k_rept_succ(int n, const int64_t* __restrict__ te, const int32_t* __restrict__ seg,
+                                                 const uint8_t* __restrict__ flags, int64_t window,
+                                                 const uint8_t* __restrict__ state, int32_t* __restrict__ succ,
+                                                 int32_t* __restrict__ exitv, int32_t* __restrict__ lastv) {
+  __shared__ int32_t sg[T];
+  __shared__ int32_t J[T];
+  __shared__ int32_t L[T];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int base = blockIdx.x * T;
+  const int g = base + tid;
+  const long long tv = g < n ? te[g] : 0;
+  const int sv = g < n ? seg[g] : -2;  // a lane behind the chunk belongs to no segment: a search stops on it
+  const uint32_t f = g < n ? flags[g] : 0u;
+  int64_t a = tv;
+  if (f & SDX_RT_SREP) a = reinterpret_cast<const sdx_repeat_timed_state_hdr*>(state)->t;
+  // the first lane behind this one that is past the anchor's window or in another segment
+  int lo = lane + 1, hi = 64;
+#pragma unroll
+  for (int it = 0; it < 7; ++it) {
+    const int mid = (lo + hi) >> 1;
+    const long long tm = __shfl(tv, mid & 63);
+    const int sm = __shfl(sv, mid & 63);
+    if (lo < hi) {
+      if (sm != sv || past(tm, a, window)) hi = mid;
+      else lo = mid + 1;
+    }
+  }
+  int s = -1;
+  if (f & SDX_RT_RB) {
+    int64_t idx = (int64_t)(g - lane) + lo;
+    if (lo >= 64) {  // behind the wave: gallop, then halve; [lo2, hi2) always holds the answer or hi2 = n
+      const int64_t a0 = idx;
+      int64_t lo2 = a0, hi2 = n;
+      for (int64_t off = 1;; off <<= 1) {
+        const int64_t p = a0 + off - 1;
+        if (p >= n) break;
+        if (seg[p] != sv || past(te[p], a, window)) {
+          hi2 = p;
+          break;
+        }
+        lo2 = p + 1;
+      }
+      while (lo2 < hi2) {
+        const int64_t mid = (lo2 + hi2) >> 1;
+        if (seg[mid] != sv || past(te[mid], a, window)) hi2 = mid;
+        else lo2 = mid + 1;
+      }
+      idx = lo2;
+    }
+    if (idx < n && seg[idx] == sv) s = (int)idx;
+  }
+  if (g < n) succ[g] = s;
+  // pointer doubling inside the tile: after round r, L = the line 2^r - 1 hops on (or the orbit's last
+  // line in the tile), J = the line 2^r hops on (T: it left the tile or ended)
+  sg[tid] = s;
+  J[tid] = (s >= 0 && s < base + T) ? s - base : T;
+  L[tid] = tid;
+#pragma unroll 1
+  for (int r = 0; r < 8; ++r) {
+    __syncthreads();
+    const int j = J[tid];
+    const int nj = j < T ? J[j] : T;
+    const int nl = j < T ? L[j] : L[tid];
+    __syncthreads();
+    J[tid] = nj;
+    L[tid] = nl;
+  }
+  __syncthreads();
+  if (g < n) {
+    const int l = L[tid];
+    lastv[g] = base + l;
+    exitv[g] = sg[l];
+  }
+}
+
+__global__ __launch_bounds__(ST) void k_rept_chain(Kinds in, int n, int nt, const sdx_repeat_key* __restrict__ keys,
+                                                   const int32_t* __restrict__ head,
+                                                   const int32_t* __restrict__ tile_head,
+                                                   const int32_t* __restrict__ exitv, const int32_t* __restrict__ lastv,
+                                                   const int64_t* __restrict__ te, const uint8_t* __restrict__ flags,
+                                                   int32_t* __restrict__ tile_arr, uint8_t* __restrict__ state) {
+  const int last_head = head[1];
+  sdx_repeat_timed_state_hdr* sh = reinterpret_cast<sdx_repeat_timed_state_hdr*>(state);
+  for (int b = threadIdx.x; b < nt; b += ST) {
+    const int h = tile_head[b];
+    if (h < 0) continue;
+    int x = h;  // only a tile's last head can have an orbit that leaves the tile
+    for (int it = 0; it < nt; ++it) {
+      const int e = exitv[x];
+      if (e < 0 || e >= n) break;
+      tile_arr[e / T] = e;
+      x = e;
+    }
+    if (h == last_head) {  // T: the last published line; it stays when the carried anchor covers them all
+      const int l = lastv[x];
+      if (!(l == h && (flags[h] & SDX_RT_SREP))) sh->t = te[l];
+    }
+  }
+  const int last = head[0];
+  if (last < 0) return;  // no result-bearing line in this chunk: the state stays
+  const uint4 v = *reinterpret_cast<const uint4*>(keys + last);
+  if (threadIdx.x == 0) {
+    sh->valid = 1;
+    sh->kind = v.x;
+    sh->proto = v.y;
+    sh->len = v.z;
+  }
+  const uint8_t* src = in.k[v.x].heap + v.w;
+  uint8_t* dst = state + sizeof(sdx_repeat_timed_state_hdr);
+  for (uint32_t i = threadIdx.x; i < v.z; i += ST) dst[i] = src[i];
+}
+
+__global__ __launch_bounds__(T) void k_rept_mark(int n, const int32_t* __restrict__ succ,
+                                                 const uint8_t* __restrict__ flags, const int32_t* __restrict__ tile_arr,
+                                                 uint8_t* __restrict__ repeat) {
+  __shared__ int32_t J[T];
+  __shared__ uint8_t on[T];
+  const int tid = threadIdx.x;
+  const int base = blockIdx.x * T;
+  const int g = base + tid;
+  const int s = g < n ? succ[g] : -1;
+  const uint32_t f = g < n ? flags[g] : 0u;
+  J[tid] = (s >= 0 && s < base + T) ? s - base : T;
+  on[tid] = 0;
+  __syncthreads();
+  if ((f & SDX_RT_HEAD) || g == tile_arr[blockIdx.x]) {
+    int x = tid;
+    for (int it = 0; it < T && x < T; ++it) {
+      on[x] = 1;
+      x = J[x];
+    }
+  }
+  __syncthreads();
+  if (g < n) repeat[g] = (f & SDX_RT_RB) ? ((on[tid] && !(f & SDX_RT_SREP)) ? 0 : 1) : 0;
+}
+
+}  // namespace sdxt
 }  // namespace sdxr
+
+extern "C" size_t sdx_repeat_timed_state_bytes(void) { return sdx_repeat_timed_state_size(); }
+extern "C" size_t sdx_repeat_timed_scratch_bytes(int32_t n) { return sdx_repeat_timed_scratch_size(n); }
+
+extern "C" int sdx_mark_repeats_timed(const sdx_bank* bank, const sdx_json_in* kinds, int k, int32_t n,
+                                      const int64_t* times_dev, int64_t window_us, uint8_t* repeat_dev,
+                                      void* scratch_dev, void* state_dev, void* hip_stream) {
+  namespace sdxt = sdxr::sdxt;
+  (void)bank;
+  if (!kinds || k < 1 || k > 4) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_timed: 1 to 4 kinds");
+  if (n < 0) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_timed: n < 0");
+  if (window_us < 0) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_timed: window_us < 0");
+  if (!times_dev || !repeat_dev || !scratch_dev || !state_dev)
+    return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_timed: null buffer");
+  if ((((uintptr_t)scratch_dev | (uintptr_t)state_dev) & 15) || ((uintptr_t)times_dev & 7))
+    return sdx::set_error(SDX_EINVAL,
+                          "sdx_mark_repeats_timed: scratch_dev and state_dev must be 16-byte, times_dev 8-byte aligned");
+  sdxr::Kinds in{};
+  for (int i = 0; i < k; ++i) {
+    const sdx_json_in& j = kinds[i];
+    if (j.kind < SDX_KIND_MU || j.kind > SDX_KIND_MN)
+      return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_timed: bad kind");
+    if (in.k[j.kind].desc) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_timed: a kind given twice");
+    if (!j.desc_dev || !j.rec_dev || !j.heap_dev)
+      return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_timed: null buffer");
+    if (j.n != n) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_timed: every kind's n must be the chunk's n");
+    in.k[j.kind] = sdxr::KindIn{j.desc_dev, j.rec_dev, j.heap_dev};
+  }
+  if (n == 0) return SDX_OK;
+  uint8_t* s = static_cast<uint8_t*>(scratch_dev);
+  int32_t* head = reinterpret_cast<int32_t*>(s);
+  sdx_repeat_key* keys = reinterpret_cast<sdx_repeat_key*>(s + sdx_rt_keys_off());
+  int64_t* te = reinterpret_cast<int64_t*>(s + sdx_rt_te_off(n));
+  int32_t* seg = reinterpret_cast<int32_t*>(s + sdx_rt_seg_off(n));
+  int32_t* succ = reinterpret_cast<int32_t*>(s + sdx_rt_succ_off(n));
+  int32_t* exitv = reinterpret_cast<int32_t*>(s + sdx_rt_exit_off(n));
+  int32_t* lastv = reinterpret_cast<int32_t*>(s + sdx_rt_last_off(n));
+  int32_t* tile_last = reinterpret_cast<int32_t*>(s + sdx_rt_tile_off(n, 0));
+  int32_t* tile_prev = reinterpret_cast<int32_t*>(s + sdx_rt_tile_off(n, 1));
+  int32_t* tile_head = reinterpret_cast<int32_t*>(s + sdx_rt_tile_off(n, 2));
+  int32_t* tile_prevhead = reinterpret_cast<int32_t*>(s + sdx_rt_tile_off(n, 3));
+  int32_t* tile_arr = reinterpret_cast<int32_t*>(s + sdx_rt_tile_off(n, 4));
+  uint8_t* flags = s + sdx_rt_flags_off(n);
+  uint8_t* state = static_cast<uint8_t*>(state_dev);
+  const int nt = (int)sdx_repeat_tiles(n);
+  hipStream_t st = (hipStream_t)hip_stream;
+  hipLaunchKernelGGL(sdxr::k_rep_keys, dim3(nt), dim3(sdxr::T), 0, st, in, (int)n, keys, tile_last);
+  hipLaunchKernelGGL(sdxr::k_rep_tiles, dim3(1), dim3(sdxr::ST), 0, st, (const int32_t*)tile_last, nt, tile_prev, head);
+  hipLaunchKernelGGL(sdxt::k_rept_heads, dim3(nt), dim3(sdxr::T), 0, st, in, (int)n, (const sdx_repeat_key*)keys,
+                     (const int32_t*)tile_prev, times_dev, window_us, (const uint8_t*)state, te, flags, tile_head,
+                     tile_arr);
+  hipLaunchKernelGGL(sdxr::k_rep_tiles, dim3(1), dim3(sdxr::ST), 0, st, (const int32_t*)tile_head, nt, tile_prevhead,
+                     head + 1);
+  hipLaunchKernelGGL(sdxt::k_rept_seg, dim3(nt), dim3(sdxr::T), 0, st, (int)n, (const uint8_t*)flags,
+                     (const int32_t*)tile_prevhead, seg);
+  hipLaunchKernelGGL(sdxt::k_rept_succ, dim3(nt), dim3(sdxr::T), 0, st, (int)n, (const int64_t*)te, (const int32_t*)seg,
+                     (const uint8_t*)flags, window_us, (const uint8_t*)state, succ, exitv, lastv);
+  hipLaunchKernelGGL(sdxt::k_rept_chain, dim3(1), dim3(sdxr::ST), 0, st, in, (int)n, nt, (const sdx_repeat_key*)keys,
+                     (const int32_t*)head, (const int32_t*)tile_head, (const int32_t*)exitv, (const int32_t*)lastv,
+                     (const int64_t*)te, (const uint8_t*)flags, tile_arr, state);
+  hipLaunchKernelGGL(sdxt::k_rept_mark, dim3(nt), dim3(sdxr::T), 0, st, (int)n, (const int32_t*)succ,
+                     (const uint8_t*)flags, (const int32_t*)tile_arr, repeat_dev);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return sdx::set_error(SDX_EHIP, std::string("sdx_mark_repeats_timed: ") + hipGetErrorString(e));
+  return SDX_OK;
+}
 
 extern "C" size_t sdx_repeat_state_bytes(void) { return sdx_repeat_state_size(); }
 extern "C" size_t sdx_repeat_scratch_bytes(int32_t n) { return sdx_repeat_scratch_size(n); }

@@ -308,24 +308,41 @@ class SignalParser:
             raise out
         return out
 
-    def parse_lines(self, lines: Sequence[Union[str, bytes]],
-                    collapse_repeats: bool = False) -> List[Union[List[DecodedMessage], Exception]]:
+    @staticmethod
+    def _window_args(collapse: bool, times, repeat_window, n: int):
+        """-> (times as int64[n], W in microseconds), (None, None) without a window; ValueError for a window
+        without collapse_repeats or without times, and for times that decrease (repeats.py)."""
+        if repeat_window is None:
+            if times is not None and len(times) != n:
+                raise ValueError(f"times: {len(times)} times for {n} lines")
+            return None, None
+        from .repeats import check_times, window_to_us
+        if not collapse:
+            raise ValueError("repeat_window needs collapse_repeats=True")
+        w = window_to_us(repeat_window)
+        return check_times(times, n), w
+
+    def parse_lines(self, lines: Sequence[Union[str, bytes]], collapse_repeats: bool = False, times=None,
+                    repeat_window: Optional[float] = None) -> List[Union[List[DecodedMessage], Exception]]:
         """Batch form of parse_line: one upload, one parse launch, one launch per demodulation
         variant, one read-back.  Returns one DecodedMessage list per line (or the ContractError
         for a line outside the device contract).  ``collapse_repeats``: a line that repeats the
         previous result-bearing line's (kind, protocol, payload) gives [] (repeats.py; the mask is
-        left in ``last_repeat_mask``)."""
+        left in ``last_repeat_mask``).  ``repeat_window`` (seconds) with ``times`` (one arrival time in
+        integer microseconds per line, non-decreasing): a run also ends once its last published line
+        is more than the window old, as FHEM dispatches (repeats.py)."""
+        times, w = self._window_args(collapse_repeats, times, repeat_window, len(lines))
         if len(lines) == 0:
             return self._collapsed([], collapse_repeats)
         data, offsets, bad = pack_lines(lines)
         return self._collapsed(self._objects(lines, LineBatch(self.protocols._ensure(), data, offsets), offsets, bad,
-                                             len(data)), collapse_repeats)
+                                             len(data)), collapse_repeats, times, w)
 
-    def _collapsed(self, out: list, collapse: bool) -> list:
+    def _collapsed(self, out: list, collapse: bool, times=None, window_us=None) -> list:
         """Object output: every payload is on the host already, so the repeats are marked there."""
         if collapse:
             from .repeats import collapse_objects
-            self.last_repeat_mask = collapse_objects(out)
+            self.last_repeat_mask = collapse_objects(out, times, window_us)
         return out
 
     def _objects(self, lines, lb: LineBatch, offsets: np.ndarray, bad: dict, nbytes: int):
@@ -514,32 +531,38 @@ class SignalParser:
 
     # ------------------------------------------------------------------------------------------
     def stream(self, chunk_lines: int = 250_000, chunk_bytes: Optional[int] = None, output: str = "json",
-               lag: int = 3, collapse_repeats: bool = False):
+               lag: int = 3, collapse_repeats: bool = False, repeat_window: Optional[float] = None):
         """A pipelined LineStream over this parser (pysignalduino_amd/stream.py): chunks of raw lines
         in, the controller's JSON texts (or the wire form) out, the PCIe copies, parse, demodulation
         and serialisation of successive chunks overlapping; the same per-line results as
         parse_lines_json / parse_lines."""
         from .stream import LineStream
         return LineStream(self, chunk_lines=chunk_lines, chunk_bytes=chunk_bytes, output=output, lag=lag,
-                          collapse_repeats=collapse_repeats)
+                          collapse_repeats=collapse_repeats, **({} if repeat_window is None else
+                                                                {"repeat_window": repeat_window}))
 
-    def parse_lines_json(self, lines: Sequence[Union[str, bytes]],
-                         collapse_repeats: bool = False) -> List[Union[Optional[str], Exception]]:
+    def parse_lines_json(self, lines: Sequence[Union[str, bytes]], collapse_repeats: bool = False, times=None,
+                         repeat_window: Optional[float] = None) -> List[Union[Optional[str], Exception]]:
         """Per line, the MQTT message text the reference controller publishes for it:
         ``MqttPublisher._message_to_json(parse_line(line)[0])`` (signalduino/controller.py:254-257,
         mqtt.py:227-245), or None when the line decodes to nothing -- parse, demodulation and JSON
         serialisation (sdx_serialize_json) all on the device; only the texts come back.
         ``collapse_repeats``: a line that repeats the previous result-bearing line's (kind, protocol,
         payload) gives None -- marked on the device (sdx_mark_repeats) and never serialised; the mask
-        is left in ``last_repeat_mask``."""
+        is left in ``last_repeat_mask``.  ``repeat_window`` (seconds) with ``times`` (one arrival time in
+        integer microseconds per line, non-decreasing; checked before anything is launched): a run also
+        ends once its last published line is more than the window old (sdx_mark_repeats_timed)."""
+        times, w = self._window_args(collapse_repeats, times, repeat_window, len(lines))
         if len(lines) == 0:
             if collapse_repeats:
                 self.last_repeat_mask = np.zeros(0, np.uint8)
             return []
         data, offsets, bad = pack_lines(lines)
-        return self._texts(lines, LineBatch(self.protocols._ensure(), data, offsets), bad, len(data), collapse_repeats)
+        return self._texts(lines, LineBatch(self.protocols._ensure(), data, offsets), bad, len(data), collapse_repeats,
+                           times, w)
 
-    def _texts(self, lines, lb: LineBatch, bad: dict, nbytes: int, collapse: bool = False):
+    def _texts(self, lines, lb: LineBatch, bad: dict, nbytes: int, collapse: bool = False, times=None,
+               window_us: Optional[int] = None):
         """parse_lines_json from the uploaded batch on (``lines`` and ``nbytes`` as in _objects)."""
         n = len(lines)
         eng = self.protocols._ensure()
@@ -610,10 +633,16 @@ class SignalParser:
                 else:
                     raise RuntimeError("result capacity overflow persists")
                 kept.append((kind, out, json_cap))
-            if kept:
+            if kept and window_us is not None:
+                rep_dev, scratch = eng.alloc_repeat_timed(n)
+                times_dev = eng.torch.from_numpy(times).to(eng.dev)
+                eng.mark_repeats_timed([eng.json_in(kind, out, lo, n) for kind, out, _ in kept], n, times_dev, window_us,
+                                       rep_dev, scratch, eng.alloc_repeat_state(timed=True))
+            elif kept:
                 rep_dev, scratch = eng.alloc_repeat(n)
                 eng.mark_repeats([eng.json_in(kind, out, lo, n) for kind, out, _ in kept], n, rep_dev, scratch,
                                  eng.alloc_repeat_state())
+            if kept:
                 for kind, out, json_cap in kept:
                     for _attempt in range(4):
                         jo = eng.alloc_json(n, json_cap)
@@ -684,7 +713,8 @@ class SignalParser:
                 return text_key(_KIND_NAME[int(kinds[i])], fetched[i]) if isinstance(fetched[i], str) else None
 
             mask = RepeatTracker().fix_chunk(rep, has_text, lambda i: text_key(_KIND_NAME[int(kinds[i])], texts[i]),
-                                             host_keys, fetch_key=fetch_key)
+                                             host_keys, fetch_key=fetch_key,
+                                             **({} if window_us is None else {"times": times, "window_us": window_us}))
             for i in sorted(set(np.nonzero(mask != rep)[0].tolist()) | set(host_keys)):
                 if mask[i]:
                     texts[i] = None      # a host-resolved repeat, or a repeat of a host-resolved line
@@ -700,7 +730,8 @@ class SignalParser:
         signalduino/transport.py:113-123).  ``final=True``: bytes after the last '\\n' are the last line
         (readline() at EOF); returns parse_lines' list for those lines.  ``final=False``: returns
         (that list for the terminated lines, the unterminated tail as bytes) -- prepend the tail to the
-        next buffer."""
+        next buffer.  There is no ``repeat_window`` here or in parse_bytes_json: one call has no per-line
+        arrival times (LineStream.submit_bytes takes one per read buffer)."""
         lines, lb, tail = self._split_bytes(data, final)
         out = self._objects(lines, lb, lines.offsets, {}, int(lines.offsets[-1])) if len(lines) else []
         out = self._collapsed(out, collapse_repeats)

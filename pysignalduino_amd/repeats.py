@@ -5,12 +5,23 @@ parse_bytes* call): a line is RESULT-BEARING when the reference's parse_line ret
 for it; its KEY is (kind, protocol, payload) of ``decoded[0]``, the message the controller publishes
 (signalduino/controller.py:252-257); it is a REPEAT when its key equals the key of the previous
 result-bearing line.  Lines without results -- noise, ignored lines, a ContractError slot, ``[]`` --
-neither start nor break a run.  There is no time-based expiry.
+neither start nor break a run.
 
-The device decides this for the lines it demodulates (sdx_mark_repeats, csrc/sdx_repeat.hip).  Lines the
+With a time window W (``repeat_window``, FHEM's dispatch rule: a telegram is dispatched again when it
+differs from the last one or more than 2 s have passed since the last one dispatched) every line has an
+arrival time, non-decreasing over the stream, and the stream carries (K, T): K the key of the previous
+result-bearing line, T the time of the last result-bearing line that was NOT marked.  A result-bearing
+line with key k and time t is a repeat when K exists, k == K and t - T <= W; otherwise it is published
+and T = t; K = k in both cases.  The anchor is the last published line, not the predecessor: with times
+0 s, 1.5 s, 2.5 s of one key and W = 2 s the third line is published.  Times are int64 microseconds;
+``repeat_window`` is given in seconds and becomes ``window_to_us(repeat_window)``.  Without a window
+there is no time-based expiry.
+
+The device decides this for the lines it demodulates (sdx_mark_repeats, with a window
+sdx_mark_repeats_timed; csrc/sdx_repeat.hip).  Lines the
 batch API resolves on the host (the general path, lines outside the contract, re-runs after an
 overflow) are invisible to it, so around them its mask can be wrong: :class:`RepeatTracker` re-decides
-exactly those places and carries the last key from chunk to chunk.  Host keys name the protocol by its
+exactly those places and carries the last key -- with a window (K, T) -- from chunk to chunk.  Host keys name the protocol by its
 id, device keys by its table index; inside one kind the two correspond one to one (bank.py).
 """
 from __future__ import annotations
@@ -45,39 +56,81 @@ def objects_key(msgs) -> Optional[Key]:
     return (str(m.raw.message_type), str(m.protocol_id), m.payload)
 
 
-def collapse_objects(out: list) -> np.ndarray:
-    """parse_lines' list with every repeat's slot replaced by [] (in place) -> the mask uint8[n]."""
+def window_to_us(repeat_window) -> Optional[int]:
+    """``repeat_window`` in seconds -> W in microseconds (None stays None)."""
+    if repeat_window is None:
+        return None
+    w = int(round(float(repeat_window) * 1e6))
+    if w < 0:
+        raise ValueError("repeat_window must not be negative")
+    return w
+
+
+def check_times(times, n: int, last: Optional[int] = None) -> np.ndarray:
+    """One call's or chunk's arrival times as int64[n]; ValueError unless there are n of them, they do not
+    decrease, and the first is not earlier than ``last`` (the previous chunk's last time)."""
+    if times is None:
+        raise ValueError("a repeat window needs the lines' arrival times (times=)")
+    t = np.asarray(times)
+    if t.dtype.kind not in "iu" or t.ndim != 1:
+        raise ValueError("times: one integer (microseconds) per line")
+    t = t.astype(np.int64, copy=False)   # an int64 array is taken as it is: the caller keeps it unchanged
+    if len(t) != n:
+        raise ValueError(f"times: {len(t)} times for {n} lines")
+    if n and (bool((t[1:] < t[:-1]).any()) or (last is not None and int(t[0]) < last)):
+        raise ValueError("times must not decrease over a stream's lines")
+    return t
+
+
+def collapse_objects(out: list, times=None, window_us: Optional[int] = None, carry: Optional[list] = None) -> np.ndarray:
+    """parse_lines' list with every repeat's slot replaced by [] (in place) -> the mask uint8[n].
+    ``window_us``: the time window W with the lines' ``times`` (microseconds); None: no expiry.
+    ``carry``: [K, T, last time] of the stream so far ([None, 0, None] starts one), updated in place: the
+    call continues that stream instead of starting one."""
+    if window_us is not None:
+        times = check_times(times, len(out), carry[2] if carry else None).tolist()
     mask = np.zeros(len(out), np.uint8)
-    prev = None
+    prev, anchor = (carry[0], carry[1]) if carry else (None, 0)
     for i, msgs in enumerate(out):
         k = objects_key(msgs)
         if k is None:
             continue
-        if k == prev:
+        if k == prev and (window_us is None or times[i] - anchor <= window_us):
             mask[i] = 1
             out[i] = []
+        elif window_us is not None:
+            anchor = times[i]
         prev = k
+    if carry:
+        carry[:] = [prev, anchor, times[-1] if window_us is not None and len(out) else carry[2]]
     return mask
 
 
 class RepeatTracker:
     """One stream's carried keys: ``true_key`` of the last result-bearing line by the definition,
-    ``dev_key`` of the last one the device saw (what its state buffer holds)."""
+    ``dev_key`` of the last one the device saw (what its state buffer holds).  With a window
+    (fix_chunk's ``times`` / ``window_us``) ``true_t`` and ``dev_t`` carry T beside them: the time of the
+    last line published by the definition, and of the last one the device left unmarked."""
 
     def __init__(self):
         self.true_key: Optional[Key] = None
         self.dev_key = None
+        self.true_t = self.dev_t = 0
 
     def fix_chunk(self, rep: np.ndarray, has_key: np.ndarray, dev_key_of: Callable[[int], Key],
                   host_keys: Dict[int, Optional[Key]], redo: Iterable[int] = (),
-                  fetch_key: Optional[Callable[[int], Optional[Key]]] = None, end_key=None) -> np.ndarray:
+                  fetch_key: Optional[Callable[[int], Optional[Key]]] = None, end_key=None,
+                  times=None, window_us: Optional[int] = None) -> np.ndarray:
         """The exact mask of a chunk.  ``rep``: the device's mask; ``has_key[i]``: dev_key_of(i) can give
         line i's key from what came back (its text, its wire records) -- a device line is
         result-bearing when has_key or rep is set; ``host_keys``: the host-resolved rows -> their key,
         None for a row without results; ``redo``: those of them the device may have seen results for
         (re-runs after an overflow); ``fetch_key(i)``: line i's key through the batch API, for a line
         the device flagged whose predecessor's key the host does not know; ``end_key``: the key the
-        device's state holds after this chunk, when the caller read it back (spares looking it up)."""
+        device's state holds after this chunk, when the caller read it back (spares looking it up);
+        ``times`` / ``window_us``: the chunk's arrival times and W, when the device ran the timed pass."""
+        if window_us is not None:
+            return self._fix_timed(rep, has_key, dev_key_of, host_keys, set(redo), fetch_key, times, window_us)
         n = len(rep)
         mask = np.array(rep, np.uint8, copy=True)
         rb = np.asarray(has_key, bool) | (mask != 0)
@@ -127,3 +180,78 @@ class RepeatTracker:
         keyed = idx[np.asarray(has_key, bool)[idx]]
         if len(keyed):
             self.true_key = self.dev_key = dev_key_of(int(keyed[-1]))
+
+    def _fix_timed(self, rep, has_key, dev_key_of, host_keys, redo, fetch_key, times, w) -> np.ndarray:
+        """fix_chunk with a window.  While the definition and the device hold the same (K, T) the device's
+        mask is exact and whole stretches are taken as they are.  From a host-resolved row on the lines are
+        re-decided one by one, the device's (K, T) followed beside the definition's, until both hold the
+        same again -- at the latest at the next line that both publish: there both hold (that key, that
+        time).  A line the device marked has its device predecessor's key."""
+        n = len(rep)
+        t = np.asarray(times)           # checked where the chunk was submitted (check_times)
+        mask = np.array(rep, np.uint8, copy=True)
+        has_key = np.asarray(has_key, bool)
+        hrows = sorted(host_keys)
+        if not hrows and self.dev_key is not UNKNOWN and (self.dev_key, self.dev_t) == (self.true_key, self.true_t):
+            # the common chunk: no host row, both sides agree -- the device's mask is exact; K is the last
+            # keyed line's key, T the last unmarked result-bearing line's time (searched from the end)
+            i = n - 1 - int(has_key[::-1].argmax()) if n else 0
+            if n and has_key[i]:
+                self.true_key = self.dev_key = dev_key_of(i)
+                pub = has_key & (mask == 0)
+                j = n - 1 - int(pub[::-1].argmax())
+                if pub[j]:
+                    self.true_t = self.dev_t = int(t[j])
+            return mask
+        rb = has_key | (mask != 0)
+        ishost = np.zeros(n, bool)
+        if hrows:
+            ishost[hrows] = True
+            rb[hrows] = False
+            mask[hrows] = 0
+        ev = np.flatnonzero(rb | ishost)      # the lines that can carry a result, in line order
+        hpos = np.searchsorted(ev, hrows)     # where the host rows stand among them
+        p, nh = 0, 0
+        while p < len(ev):
+            if self.dev_key is not UNKNOWN and (self.dev_key, self.dev_t) == (self.true_key, self.true_t):
+                while nh < len(hpos) and hpos[nh] < p:
+                    nh += 1
+                q = int(hpos[nh]) if nh < len(hpos) else len(ev)
+                if q > p:   # device lines in agreement: K = the last keyed line's, T = the last unmarked line's
+                    span = ev[p:q]
+                    keyed = span[has_key[span]]
+                    if len(keyed):
+                        self.true_key = self.dev_key = dev_key_of(int(keyed[-1]))
+                    pub = span[mask[span] == 0]
+                    if len(pub):
+                        self.true_t = self.dev_t = int(t[pub[-1]])
+                    p = q
+                    continue
+            i = int(ev[p])
+            p += 1
+            if ishost[i]:
+                k = host_keys[i]
+                if i in redo:   # the device may have seen a result here: what it holds is not known
+                    self.dev_key = self.dev_t = UNKNOWN
+            else:
+                if has_key[i]:
+                    k = dev_key_of(i)
+                else:       # marked by the device, no text: the key of the device's predecessor
+                    k = self.dev_key
+                    if k is UNKNOWN or k is None:
+                        if fetch_key is None:
+                            raise RuntimeError(f"line {i}: a flagged line whose key is unknown and no fetch_key")
+                        k = fetch_key(i)
+                if k is not None:
+                    self.dev_key = k
+                    if not rep[i]:
+                        self.dev_t = int(t[i])
+            if k is None:
+                continue
+            if self.true_key is not None and k == self.true_key and int(t[i]) - self.true_t <= w:
+                mask[i] = 1
+            else:
+                mask[i] = 0
+                self.true_t = int(t[i])
+            self.true_key = k
+        return mask

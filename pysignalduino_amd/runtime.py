@@ -48,7 +48,8 @@ EXPORTED = ["sdx_abi_version", "sdx_last_error", "sdx_source_hash", "sdx_layout_
             "sdx_lines_general", "sdx_lines_exact", "sdx_parse_floats", "sdx_format_floats", "sdx_copy_async", "sdx_copy_async_kind", "sdx_copy_async_narrow",
             "sdx_fill_async", "sdx_demod_step", "sdx_group_step", "sdx_split_work_bytes", "sdx_split_lines",
             "sdx_host_count_byte", "sdx_serialize_json_skip", "sdx_mark_repeats", "sdx_repeat_state_bytes",
-            "sdx_repeat_scratch_bytes", "sdx_repeat_tile"]
+            "sdx_repeat_scratch_bytes", "sdx_repeat_tile", "sdx_mark_repeats_timed", "sdx_repeat_timed_state_bytes",
+            "sdx_repeat_timed_scratch_bytes"]
 GROUP_MIN = int(os.environ.get("SDX_GROUP_MIN", "4096"))   # SDX_GROUP_MIN (the env: A/B of the grouping)
 
 
@@ -245,6 +246,13 @@ def load_library(path: Optional[str] = None):
     lib.sdx_repeat_scratch_bytes.restype = c_size_t
     lib.sdx_repeat_tile.argtypes = []
     lib.sdx_repeat_tile.restype = c_int
+    lib.sdx_mark_repeats_timed.argtypes = [c_void_p, POINTER(SdxJsonIn), c_int, c_int32, c_void_p, ctypes.c_int64, c_void_p,
+                                           c_void_p, c_void_p, c_void_p]
+    lib.sdx_mark_repeats_timed.restype = c_int
+    lib.sdx_repeat_timed_state_bytes.argtypes = []
+    lib.sdx_repeat_timed_state_bytes.restype = c_size_t
+    lib.sdx_repeat_timed_scratch_bytes.argtypes = [c_int32]
+    lib.sdx_repeat_timed_scratch_bytes.restype = c_size_t
     lib.sdx_parse_lines.argtypes = [POINTER(SdxLines), POINTER(SdxLinesOut), c_void_p]
     lib.sdx_parse_lines.restype = c_int
     lib.sdx_select_lines.argtypes = [POINTER(SdxLinesOut), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
@@ -699,10 +707,12 @@ class Engine:
     def repeat_tile(self) -> int:
         return int(self.lib.sdx_repeat_tile())
 
-    def alloc_repeat_state(self):
-        """The carried state of one stream of lines, zeroed: no previous result-bearing line."""
+    def alloc_repeat_state(self, timed: bool = False):
+        """The carried state of one stream of lines, zeroed: no previous result-bearing line.
+        ``timed``: the state of mark_repeats_timed (a layout of its own: header, T, payload)."""
         t = self.torch
-        return t.zeros(int(self.lib.sdx_repeat_state_bytes()), dtype=t.uint8, device=self.dev)
+        size = self.lib.sdx_repeat_timed_state_bytes() if timed else self.lib.sdx_repeat_state_bytes()
+        return t.zeros(int(size), dtype=t.uint8, device=self.dev)
 
     def alloc_repeat(self, n: int):
         """(repeat mask uint8[n], key scratch) for chunks of up to n lines."""
@@ -725,6 +735,31 @@ class Engine:
         st = self.stream_ptr() if stream is None else c_void_p(stream.cuda_stream)
         _check(self.lib, self.lib.sdx_mark_repeats(self.handle, arr, len(json_ins), n, _ptr(repeat), _ptr(scratch),
                                                    _ptr(state), st))
+
+    def alloc_repeat_timed(self, n: int):
+        """(repeat mask uint8[n], scratch) of mark_repeats_timed for chunks of up to n lines."""
+        t = self.torch
+        return (t.zeros(max(n, 1), dtype=t.uint8, device=self.dev),
+                t.empty(int(self.lib.sdx_repeat_timed_scratch_bytes(max(n, 1))), dtype=t.uint8, device=self.dev))
+
+    def mark_repeats_timed(self, json_ins, n: int, times, window_us: int, repeat, scratch, state, stream=None) -> None:
+        """sdx_mark_repeats_timed on ``stream`` (default: the current one; no host sync): mark_repeats where a
+        run also ends once its last published line is more than ``window_us`` old.  ``times``: a device
+        int64 tensor, one arrival time in microseconds per line, non-decreasing (a precondition the caller
+        checks: frontend / stream do); ``scratch``: alloc_repeat_timed's; ``state``:
+        alloc_repeat_state(timed=True) of this stream of lines."""
+        n = int(n)
+        if not 1 <= len(json_ins) <= 4:
+            raise ValueError("mark_repeats_timed: 1 to 4 kinds")
+        if (repeat.numel() * repeat.element_size() < n or
+                (times is not None and times.numel() * times.element_size() < 8 * n) or
+                scratch.numel() * scratch.element_size() < int(self.lib.sdx_repeat_timed_scratch_bytes(n)) or
+                state.numel() * state.element_size() < int(self.lib.sdx_repeat_timed_state_bytes())):
+            raise ValueError("mark_repeats_timed: a buffer is too small for n")
+        arr = (SdxJsonIn * len(json_ins))(*json_ins)
+        st = self.stream_ptr() if stream is None else c_void_p(stream.cuda_stream)
+        _check(self.lib, self.lib.sdx_mark_repeats_timed(self.handle, arr, len(json_ins), n, _ptr(times), int(window_us),
+                                                         _ptr(repeat), _ptr(scratch), _ptr(state), st))
 
     def alloc_json(self, items: int, cap: int):
         t, d = self.torch, self.dev

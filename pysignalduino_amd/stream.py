@@ -279,7 +279,11 @@ class _Slot:
             self.h_sizes = t.zeros(runtime.XCHG_COUNTS * len(self.outs) + 4 * len(self.outs), dtype=t.int32).pin_memory()
             cap = sum(16 * C + 8 * o["rec_cap"] + o["heap_cap"] + 64 for o in self.outs.values())
             self.h_out = t.empty(cap + 3 * C + 64, dtype=t.uint8).pin_memory()
-        if ls.collapse:   # the repeat mask, sdx_mark_repeats' scratch, and the state's head read back per chunk
+        if ls.collapse and ls.window_us is not None:   # the timed pass: its scratch, the chunk's arrival times
+            self.rep, self.rep_scratch = eng.alloc_repeat_timed(C)
+            self.d_times = t.zeros(C, dtype=t.int64, device=eng.dev)
+            self.h_times = t.zeros(C, dtype=t.int64).pin_memory()
+        elif ls.collapse:   # the repeat mask, sdx_mark_repeats' scratch, and the state's head read back per chunk
             self.rep, self.rep_scratch = eng.alloc_repeat(C)
             self.h_state = t.zeros(_STATE_HEAD, dtype=t.uint8).pin_memory()
         self.reset()
@@ -291,13 +295,17 @@ class _Slot:
         self.lines = None
         self.ev = None
         self.src = None           # a submit_bytes chunk: its _ChunkBytes (the offsets come back in stage C)
+        self.times = None         # repeat_window: the chunk's arrival times, int64[n] (a host copy for _fix_repeats)
 
 
 class LineStream:
     """See the module docstring.  ``parser``: a frontend.SignalParser; ``chunk_lines`` /
     ``chunk_bytes``: the capacity of one chunk; ``output``: "json" (the controller's publication) or
     "wire" (per line and kind the exchange's wire form); ``lag``: chunks the host stays behind the
-    GPU (slots = lag + 1).
+    GPU (slots = lag + 1); ``collapse_repeats`` / ``repeat_window`` (seconds): repeat suppression, with a
+    window every submit carries arrival times in integer microseconds, non-decreasing over the stream
+    (repeats.py): ``submit(lines, times=)`` and ``submit_packed(..., times=)`` one per line,
+    ``submit_bytes(buf, time=)`` one per read buffer.
 
     submit(lines) -> chunk id; ``submit_packed(data, offsets)`` the same for lines already packed as
     (uint8 bytes, int64 offsets[n + 1]); ``submit_bytes(buf)`` -> chunk ids for a transport's raw read
@@ -306,10 +314,15 @@ class LineStream:
     order (never blocks on a chunk newer than ``lag`` submits); drain() -> all of them (blocks)."""
 
     def __init__(self, parser, chunk_lines: int = 250_000, chunk_bytes: Optional[int] = None, output: str = "json",
-                 lag: int = 3, collapse_repeats: bool = False):
+                 lag: int = 3, collapse_repeats: bool = False, repeat_window: Optional[float] = None):
         if output not in ("json", "wire"):
             raise ValueError("output must be 'json' or 'wire'")
         self.collapse = bool(collapse_repeats)
+        from .repeats import window_to_us
+        self.window_us = window_to_us(repeat_window)
+        if self.window_us is not None and not self.collapse:
+            raise ValueError("repeat_window needs collapse_repeats=True")
+        self._last_time = None    # repeat_window: the last submitted line's time
         import torch
         self.torch = torch
         self.parser = parser
@@ -324,7 +337,8 @@ class LineStream:
             # repeat suppression: ONE state per stream, written by every chunk's state pass;
             # rep_ev orders the next chunk's sdx_mark_repeats (on the other demodulation stream) behind it
             from .repeats import RepeatTracker
-            self.rep_state = self.eng.alloc_repeat_state()
+            self.rep_state = (self.eng.alloc_repeat_state() if self.window_us is None else
+                              self.eng.alloc_repeat_state(timed=True))
             self.rep_ev = None
             self.tracker = RepeatTracker()
         self.slots = [_Slot(self) for _ in range(self.lag + 1)]
@@ -349,20 +363,34 @@ class LineStream:
         self._carry = bytearray()  # submit_bytes: the unterminated tail of the calls so far
 
     # -- public ------------------------------------------------------------------------------------------
-    def submit(self, lines: Sequence[Union[str, bytes]]) -> int:
+    def submit(self, lines: Sequence[Union[str, bytes]], times=None) -> int:
         from .frontend import pack_lines
+        times = self._check_times(times, len(lines))   # before anything is packed or launched
         data, offsets, bad = pack_lines(lines, copy=False)   # read once, into the slot's pinned buffer
-        return self.submit_packed(data, offsets, lines=lines, bad=bad)
+        return self.submit_packed(data, offsets, lines=lines, bad=bad, times=times)
 
-    def submit_packed(self, data, offsets: np.ndarray, lines=None, bad=None) -> int:
+    def _check_times(self, times, n: int):
+        """A chunk's arrival times as int64[n] (None without a window); ValueError when they are missing,
+        decrease, or start before the previous chunk's last one."""
+        if self.window_us is None:
+            if times is not None:
+                raise ValueError("times given, but the stream has no repeat_window")
+            return None
+        from .repeats import check_times
+        return check_times(times, n, self._last_time)
+
+    def submit_packed(self, data, offsets: np.ndarray, lines=None, bad=None, times=None) -> int:
         """``data``: the lines' bytes as a numpy uint8 array (copied into the slot's pinned buffer) or
         a PINNED torch uint8 tensor (uploaded from where it is, no host copy: keep it unchanged until
-        the chunk has been collected); ``offsets``: int64[n + 1] into it."""
+        the chunk has been collected); ``offsets``: int64[n + 1] into it; ``times``: with a
+        ``repeat_window``, the n arrival times (integer microseconds)."""
         n = len(offsets) - 1
         if n > self.C or int(offsets[-1] - offsets[0]) > self.B:
             raise ValueError(f"chunk of {n} lines / {int(offsets[-1] - offsets[0])} bytes exceeds the stream's "
                              f"capacity ({self.C} lines, {self.B} bytes)")
+        times = self._check_times(times, n)
         s = self._take_slot(n)
+        self._set_times(s, times)
         s.lines, s.bad = lines, bad or {}
         s.data, s.offsets = data, offsets
         self._stage_a(s, data, offsets)
@@ -379,6 +407,22 @@ class LineStream:
         self.next_id += 1
         return s
 
+    def _set_times(self, s: _Slot, times) -> None:
+        """The chunk's checked times into its slot's pinned buffer (stage A uploads them with the chunk)."""
+        s.times = None
+        if times is not None:
+            n = len(times)
+            s.times = s.h_times.numpy()[:n]     # the slot's own copy: the caller's array may change
+            s.times[:] = times
+            if n:
+                self._last_time = int(times[-1])
+
+    def _upload_times(self, s: _Slot) -> None:
+        """On the input stream, in front of the chunk's h2d event: 8 bytes per line."""
+        if s.times is not None and s.n:
+            runtime.copy_async(s.d_times[: s.n], s.h_times[: s.n], self.cin)
+            self.h2d_bytes += 8 * s.n
+
     def _queued(self, s: _Slot) -> int:
         self.inflight.append(s)
         # the chunks behind: stage B for the previous one, C for the one before, collect the oldest
@@ -387,7 +431,7 @@ class LineStream:
                 self._advance(self.inflight[-1 - age], want)
         return s.cid
 
-    def submit_bytes(self, buf, final: bool = False) -> List[int]:
+    def submit_bytes(self, buf, final: bool = False, time: Optional[int] = None) -> List[int]:
         """A transport's read buffer, raw: ``buf`` is bytes-like (copied into the slot's pinned buffer) or
         a PINNED torch uint8 tensor (uploaded from where it is: keep it unchanged until its chunks have
         been collected), of any size.  Every '\\n' ends a line (StreamReader.readline(),
@@ -396,8 +440,23 @@ class LineStream:
         The unterminated tail is carried into the next call; ``final=True`` (or close_bytes()) makes a
         non-empty tail the last line.  Returns the ids of the chunks queued (none, one or several).  A
         line longer than ``chunk_bytes`` raises ValueError: the chunks cut in front of it stay queued, the
-        line and what follows it in ``buf`` are not taken."""
+        line and what follows it in ``buf`` are not taken.  ``time``: with a ``repeat_window``, the arrival
+        time of this read buffer (integer microseconds, not earlier than the previous one's).  A line gets
+        the time of the buffer that holds its terminating newline -- when StreamReader.readline() would
+        have returned it --, an unterminated tail made the last line the time of the last buffer."""
         t = self.torch
+        if self.window_us is None:
+            if time is not None:
+                raise ValueError("time given, but the stream has no repeat_window")
+        else:
+            if time is None and len(buf):   # an empty buffer ends no line: close_bytes() needs no time
+                raise ValueError("a repeat window needs the read buffer's arrival time (time=)")
+            if time is not None:
+                if int(time) != time:
+                    raise ValueError("time: integer microseconds")
+                if self._last_time is not None and int(time) < self._last_time:
+                    raise ValueError("times must not decrease over a stream's lines")
+                self._last_time = int(time)
         if isinstance(buf, (bytes, bytearray)):
             arr = np.frombuffer(buf, np.uint8)
             view = buf if len(buf) <= 2 * _NlView.PART else _NlView(arr)   # a read buffer: bytes' own rfind / count
@@ -426,6 +485,7 @@ class LineStream:
         s = self._take_slot(n)
         s.lines, s.bad = None, {}
         s.data = s.offsets = None
+        self._set_times(s, None if self.window_us is None else np.full(n, self._last_time, np.int64))
         self._stage_a_bytes(s, np.frombuffer(bytes(carry), np.uint8), pinned_buf, arr, lo, hi, final)
         return self._queued(s)
 
@@ -486,6 +546,7 @@ class LineStream:
                 s.h_bytes.numpy()[nb: nb + 16] = 0
                 runtime.copy_async(lb.bytes[: nb + 16], s.h_bytes[: nb + 16], self.cin)
             runtime.copy_async(lb.offsets[: n + 1], s.h_offs[: n + 1], self.cin)
+            self._upload_times(s)
             h2d = t.cuda.Event()
             h2d.record(self.cin)
         self.h2d_bytes += nb + 8 * (n + 1)
@@ -530,6 +591,7 @@ class LineStream:
                     runtime.copy_async(lb.bytes[:cl], s.h_bytes[:cl], self.cin)
                 lb.bytes[cl:nb].copy_(pinned_buf[lo:hi], non_blocking=True)
                 runtime.fill_async(lb.bytes[nb: nb + 16], self.cin)
+            self._upload_times(s)
             h2d = t.cuda.Event()
             h2d.record(self.cin)
         self.h2d_bytes += nb
@@ -618,9 +680,13 @@ class LineStream:
                 # demodulation stream); this chunk's demodulation above is already enqueued beside it
                 if self.rep_ev is not None:
                     sd.wait_event(self.rep_ev)
-                eng.mark_repeats([eng.json_in(kd, s.outs[name], lo, n, 2) for name, kd, _, _ in _KINDS if name in s.outs],
-                                 n, s.rep, s.rep_scratch, self.rep_state, stream=sd)
-                runtime.copy_async(s.h_state, self.rep_state[:_STATE_HEAD], sd)
+                ins = [eng.json_in(kd, s.outs[name], lo, n, 2) for name, kd, _, _ in _KINDS if name in s.outs]
+                if self.window_us is None:
+                    eng.mark_repeats(ins, n, s.rep, s.rep_scratch, self.rep_state, stream=sd)
+                    runtime.copy_async(s.h_state, self.rep_state[:_STATE_HEAD], sd)
+                else:   # the chunk's times came up with its bytes (stage A, in front of the parse)
+                    eng.mark_repeats_timed(ins, n, s.d_times, self.window_us, s.rep, s.rep_scratch, self.rep_state,
+                                           stream=sd)
                 self.rep_ev = t.cuda.Event()
                 self.rep_ev.record(sd)
             if self.output == "json":
@@ -686,7 +752,7 @@ class LineStream:
             s.kb = b
             if self.collapse:
                 runtime.copy_async(ho[b + 2 * n: b + 3 * n], s.rep[:n], self.cout)
-                self.d2h_bytes += n + _STATE_HEAD
+                self.d2h_bytes += n + (_STATE_HEAD if self.window_us is None else 0)
             if s.src is not None:   # a submit_bytes chunk: the offsets the device found, for line(i)
                 runtime.copy_async(s.h_offs[: n + 1], lb.offsets[: n + 1], self.cout)
                 self.d2h_bytes += 8 * (n + 1)
@@ -771,6 +837,11 @@ class LineStream:
                 return text_key(name_of(i), bytes(blob[o: o + int(r.len[i])]).decode("ascii"))
         else:
             has_key, dev_key_of = self._wire_keys(r)
+        if self.window_us is not None:   # the tracker follows (K, T) from the mask, the keys and the times
+            mask = self.tracker.fix_chunk(rep, has_key, dev_key_of, host_keys, redo, fetch, times=s.times,
+                                          window_us=self.window_us)
+            self._apply_mask(s, r, rep, mask, host_keys, fetched)
+            return
         # what the device's state held after this chunk (read back behind its state pass)
         hs = s.h_state.numpy()
         valid, kd, proto, ln = (int(x) for x in hs[:16].view(np.uint32))
@@ -779,8 +850,11 @@ class LineStream:
             pids = (self.bank.mu_pids, self.bank.ms_pids, self.bank.mc_pids, self.bank.mn_pids)[kd]
             end_key = (("MU", "MS", "MC", "MN")[kd], str(pids[proto]), hs[16: 16 + ln].tobytes().decode("latin-1"))
         mask = self.tracker.fix_chunk(rep, has_key, dev_key_of, host_keys, redo, fetch, end_key)
+        self._apply_mask(s, r, rep, mask, host_keys, fetched)
+
+    def _apply_mask(self, s: _Slot, r: ChunkResult, rep, mask, host_keys, fetched) -> None:
         r.repeat = mask
-        if not js:
+        if self.output != "json":
             return
         for i in sorted(set(np.nonzero(mask != rep)[0].tolist()) | set(host_keys)):
             if mask[i]:

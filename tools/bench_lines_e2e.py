@@ -105,7 +105,13 @@ def main():
     ap.add_argument("--repeat", type=int, default=1, help="emit each synthetic line R times consecutively (as a stick "
                     "delivers telegrams): --lines / R distinct lines, --lines lines in all")
     ap.add_argument("--collapse", action="store_true", help="stream with collapse_repeats=True (repeats are never serialised)")
+    ap.add_argument("--window", type=float, default=None, metavar="SECONDS",
+                    help="with --collapse: stream with repeat_window=SECONDS; the lines get synthetic, evenly spaced "
+                         "arrival times (SECONDS / 8 apart, so a burst of --repeat 4 stays inside the window; they run "
+                         "on over the passes)")
     args = ap.parse_args()
+    if args.window is not None and not args.collapse:
+        ap.error("--window needs --collapse")
     import torch
     from pysignalduino_amd import frontend, runtime, synth
     from pysignalduino_amd.sd_protocols import SDProtocols
@@ -129,6 +135,11 @@ def main():
         src = np.repeat(offsets[:-1][idx] - new_off[:-1], lens) + np.arange(int(new_off[-1]))
         data, offsets = data[src], new_off
     ckw = {"collapse_repeats": True} if args.collapse else {}
+    timed = args.window is not None
+    if timed:
+        ckw["repeat_window"] = args.window
+        spacing_us = int(round(args.window / 8 * 1e6))
+    marked = [0, 0]   # --window: repeats marked, lines seen (over all results)
     C = args.chunk
     nck = (len(offsets) - 1) // C
     assert nck >= 2, "need at least two chunks"
@@ -154,10 +165,25 @@ def main():
         ls = sp.stream(chunk_lines=C + C // 10 + 16, chunk_bytes=step + 65536, output=args.output, lag=args.lag,
                        **ckw)
         submit = ls.submit_bytes
+        if timed:   # one time per read buffer: that of the last line it ends
+            clock = [0]
+
+            def submit(piece):   # noqa: F811
+                clock[0] += C * spacing_us
+                return ls.submit_bytes(piece, time=clock[0])
     else:
         feed = chunks
         ls = sp.stream(chunk_lines=C, chunk_bytes=maxb, output=args.output, lag=args.lag, **ckw)
         submit = lambda ch: ls.submit_packed(*ch)   # noqa: E731
+        if timed:   # one time per line, evenly spaced, running on from chunk to chunk
+            ramp = np.arange(C, dtype=np.int64) * spacing_us
+            tbuf = np.empty(C, np.int64)    # one buffer: the stream copies a chunk's times as it takes them
+            clock = [0]
+
+            def submit(ch):   # noqa: F811
+                np.add(ramp, clock[0], out=tbuf)
+                clock[0] += C * spacing_us
+                return ls.submit_packed(*ch, times=tbuf)
     # warm-up: one pass through every stage (kernels loaded, buffers touched)
     for ch in feed:
         submit(ch)
@@ -179,12 +205,18 @@ def main():
         h0 = time.perf_counter()
         submit(feed[k % nck])
         for r in ls.poll():
+            if timed:
+                marked[0] += int(np.count_nonzero(r.repeat))
+                marked[1] += r.n
             if first is None and args.check:
                 first = r.detach()
             if args.bytes and args.check and sum(x.n for x in head) < C:
                 head.append(r.detach())
         host_t += time.perf_counter() - h0
     for r in ls.drain():
+        if timed:
+            marked[0] += int(np.count_nonzero(r.repeat))
+            marked[1] += r.n
         if first is None and args.check:
             first = r.detach()
         if args.bytes and args.check and sum(x.n for x in head) < C:
@@ -214,6 +246,8 @@ def main():
                   "in pinned host memory (PCIe both ways, overlapped; SignalParser.stream)",
         "value": total / dt, "unit": "lines/s", "n_gpus": 1, "lines": total, "chunk_lines": C, "lag": args.lag,
         "repeat": args.repeat, "collapse": bool(args.collapse),
+        **({"repeat_window_s": args.window, "time_spacing_us": spacing_us, "repeats_marked": marked[0],
+            "lines_seen": marked[1]} if timed else {}),
         "output": args.output, "input": "bytes" if args.bytes else "packed", "chunks": nsteps, "ms_per_chunk": 1e3 * per_chunk,
         "kernels_ms_per_chunk": {"parse+select": 1e3 * k_parse, "demod+serialise": 1e3 * k_demod},
         "chunk_span_ms_median": 1e3 * float(np.median(span)),
