@@ -513,6 +513,32 @@ int sdx_mark_repeats_timed(const sdx_bank* bank, const sdx_json_in* kinds, int k
                            const int64_t* times_dev, int64_t window_us, uint8_t* repeat_dev, void* scratch_dev,
                            void* state_dev, void* hip_stream);
 
+/* Repeat suppression for a stream that merges several receivers: one (K, T) per source id.
+ * source_dev[line]: the line's source id (int32), 0 <= id < n_sources, 1 <= n_sources <=
+ * SDX_REPEAT_SOURCES_MAX (4096).  For each source the subsequence of the chunk's lines with that id, in
+ * line order, is decided as a stream of its own by the definitions above: lines of other sources neither
+ * start, break nor time out a run.  times_dev = NULL: no window (sdx_mark_repeats' rule per source,
+ * window_us is not read); otherwise sdx_mark_repeats_timed's rule per source with W = window_us.
+ * state_dev: sdx_repeat_sources_state_bytes(n_sources) bytes, 16-byte aligned: n_sources slots of
+ * sdx_repeat_timed_state_bytes() bytes, each with the timed state's layout; zeroing a slot's header starts
+ * that source, a source without a result-bearing line in the chunk keeps its slot untouched.  With
+ * n_sources = 1 the mask and slot 0 equal sdx_mark_repeats_timed's (without times: sdx_mark_repeats' mask).
+ * scratch_dev: sdx_repeat_sources_scratch_bytes(n, n_sources) bytes, 16-byte aligned; after the call its
+ * part SDX_RS_TABLE (csrc/sdx_repeat_layout.h) holds one sdx_repeat_source_entry per source: the slot's
+ * header and the source's last result-bearing line of this chunk.  No allocation, no synchronisation, no
+ * spinning, no global atomics; every entry of repeat_dev[0, n) is written.  PRECONDITIONS: every id is
+ * inside [0, n_sources) and the times do not decrease WITHIN a source (they may across sources).  On other
+ * input the mask is unspecified, but a line with an id outside the range gets mask 0 and touches no slot,
+ * and every kernel stays inside its buffers and ends.  SDX_EINVAL (nothing launched): a null buffer,
+ * n_sources outside 1 .. 4096, window_us < 0 with times, a misaligned scratch_dev / state_dev (16 bytes),
+ * times_dev (8) or source_dev (4), bad kinds. */
+size_t sdx_repeat_sources_state_bytes(int32_t n_sources);
+size_t sdx_repeat_sources_scratch_bytes(int32_t n, int32_t n_sources);
+int sdx_mark_repeats_by_source(const sdx_bank* bank, const sdx_json_in* kinds, int k, int32_t n,
+                               const int32_t* source_dev, int32_t n_sources, const int64_t* times_dev,
+                               int64_t window_us, uint8_t* repeat_dev, void* scratch_dev, void* state_dev,
+                               void* hip_stream);
+
 /* ---- unit-level entry ------------------------------------------------------------------------
  * The reference's helper methods that its own unit tests call on SDProtocols, evaluated on n
  * independent inputs in one launch (lane = item), with the device code the demodulation kernels

@@ -15,7 +15,8 @@
 //   k_rep_state    one workgroup: key + payload of the chunk's last result-bearing line -> state
 // Payload bytes are read one at a time, [off, off + len) only: nothing past a payload's end.
 // sdx_mark_repeats_timed (a run also ends when its last published line is too old) follows below, with
-// kernels of its own behind k_rep_keys and k_rep_tiles.
+// kernels of its own behind k_rep_keys and k_rep_tiles; sdx_mark_repeats_by_source (one run per source id of
+// a stream that merges several receivers) sorts the lines by id and runs the timed kernels over the result.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -211,12 +212,31 @@ __device__ __forceinline__ bool past(int64_t t, int64_t anchor, int64_t w) {
   return (uint64_t)t - (uint64_t)anchor > (uint64_t)w;
 }
 
+// sdx_mark_repeats_by_source runs these passes over POSITIONS (the lines sorted by source id, stable), BS =
+// true; the two entries above it instantiate BS = false, where the struct is not read.
+struct BySrc {
+  const uint32_t* psrc;  // the position's source id, < S
+  const int32_t* perm;   // position -> line
+  int32_t* ipred;        // out: the last result-bearing position at or in front of the position
+  int S;
+};
+template <bool BS>
+__device__ __forceinline__ const uint8_t* slot_of(const uint8_t* state, const BySrc& bs, int g) {
+  if constexpr (BS) {
+    const uint32_t s = bs.psrc[g];
+    return state + (size_t)(s < (uint32_t)bs.S ? s : 0u) * SDX_REPEAT_TIMED_STATE_SIZE;
+  } else {
+    return state;
+  }
+}
+
+template <bool BS>
 __global__ __launch_bounds__(T) void k_rept_heads(Kinds in, int n, const sdx_repeat_key* __restrict__ keys,
                                                   const int32_t* __restrict__ tile_prev,
                                                   const int64_t* __restrict__ times, int64_t window,
                                                   const uint8_t* __restrict__ state, int64_t* __restrict__ te,
                                                   uint8_t* __restrict__ flags, int32_t* __restrict__ tile_head,
-                                                  int32_t* __restrict__ tile_arr) {
+                                                  int32_t* __restrict__ tile_arr, BySrc bs) {
   __shared__ int32_t wlast[WAVES];
   __shared__ int32_t whead[WAVES];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -241,20 +261,26 @@ __global__ __launch_bounds__(T) void k_rept_heads(Kinds in, int n, const sdx_rep
       if (pred < 0) pred = tile_prev[blockIdx.x];
     }
     int64_t t = 0;
+    bool inrun = pred >= 0;  // the predecessor decides; otherwise the carried state
+    if constexpr (BS) {
+      bs.ipred[g] = have ? g : pred;
+      inrun = inrun && bs.psrc[pred] == bs.psrc[g];  // a source's first result-bearing line: its own state
+    }
     if (have) {
       t = times[g];
       f = SDX_RT_RB;
       const uint8_t* mine = in.k[key.kind].heap + key.off;
-      if (pred >= 0) {
+      if (inrun) {
         const uint4 v = *reinterpret_cast<const uint4*>(keys + pred);
         const bool cont = !past(t, times[pred], window) && v.x == key.kind && v.y == key.proto && v.z == key.len &&
                           same_bytes(mine, in.k[key.kind].heap + v.w, key.len);
         if (!cont) f |= SDX_RT_HEAD;
       } else {  // the chunk's first result-bearing line: the carried (K, T)
-        const sdx_repeat_timed_state_hdr h = *reinterpret_cast<const sdx_repeat_timed_state_hdr*>(state);
+        const uint8_t* slot = slot_of<BS>(state, bs, g);
+        const sdx_repeat_timed_state_hdr h = *reinterpret_cast<const sdx_repeat_timed_state_hdr*>(slot);
         f |= SDX_RT_HEAD;
         if (h.valid && !past(t, h.t, window) && h.kind == key.kind && h.proto == key.proto && h.len == key.len &&
-            same_bytes(mine, state + sizeof(sdx_repeat_timed_state_hdr), key.len))
+            same_bytes(mine, slot + sizeof(sdx_repeat_timed_state_hdr), key.len))
           f |= SDX_RT_SREP;
       }
     } else if (pred >= 0) {
@@ -296,10 +322,11 @@ __global__ __launch_bounds__(T) void k_rept_seg(int n, const uint8_t* __restrict
   seg[g] = s;
 }
 
+template <bool BS>
 __global__ __launch_bounds__(T) void k_rept_succ(int n, const int64_t* __restrict__ te, const int32_t* __restrict__ seg,
                                                  const uint8_t* __restrict__ flags, int64_t window,
                                                  const uint8_t* __restrict__ state, int32_t* __restrict__ succ,
-                                                 int32_t* __restrict__ exitv, int32_t* __restrict__ lastv) {
+                                                 int32_t* __restrict__ exitv, int32_t* __restrict__ lastv, BySrc bs) {
   __shared__ int32_t sg[T];
   __shared__ int32_t J[T];
   __shared__ int32_t L[T];
@@ -310,7 +337,7 @@ __global__ __launch_bounds__(T) void k_rept_succ(int n, const int64_t* __restric
   const int sv = g < n ? seg[g] : -2;  // a lane behind the chunk belongs to no segment: a search stops on it
   const uint32_t f = g < n ? flags[g] : 0u;
   int64_t a = tv;
-  if (f & SDX_RT_SREP) a = reinterpret_cast<const sdx_repeat_timed_state_hdr*>(state)->t;
+  if (f & SDX_RT_SREP) a = reinterpret_cast<const sdx_repeat_timed_state_hdr*>(slot_of<BS>(state, bs, g))->t;
   // the first lane behind this one that is past the anchor's window or in another segment
   int lo = lane + 1, hi = 64;
 #pragma unroll
@@ -371,6 +398,7 @@ __global__ __launch_bounds__(T) void k_rept_succ(int n, const int64_t* __restric
   }
 }
 
+template <bool BS>
 __global__ __launch_bounds__(ST) void k_rept_chain(Kinds in, int n, int nt, const sdx_repeat_key* __restrict__ keys,
                                                    const int32_t* __restrict__ head,
                                                    const int32_t* __restrict__ tile_head,
@@ -389,11 +417,12 @@ __global__ __launch_bounds__(ST) void k_rept_chain(Kinds in, int n, int nt, cons
       tile_arr[e / T] = e;
       x = e;
     }
-    if (h == last_head) {  // T: the last published line; it stays when the carried anchor covers them all
+    if (!BS && h == last_head) {  // T: the last published line; it stays when the carried anchor covers them all
       const int l = lastv[x];
       if (!(l == h && (flags[h] & SDX_RT_SREP))) sh->t = te[l];
     }
   }
+  if constexpr (BS) return;  // the sources' slots: k_reps_state
   const int last = head[0];
   if (last < 0) return;  // no result-bearing line in this chunk: the state stays
   const uint4 v = *reinterpret_cast<const uint4*>(keys + last);
@@ -408,9 +437,10 @@ __global__ __launch_bounds__(ST) void k_rept_chain(Kinds in, int n, int nt, cons
   for (uint32_t i = threadIdx.x; i < v.z; i += ST) dst[i] = src[i];
 }
 
+template <bool BS>
 __global__ __launch_bounds__(T) void k_rept_mark(int n, const int32_t* __restrict__ succ,
                                                  const uint8_t* __restrict__ flags, const int32_t* __restrict__ tile_arr,
-                                                 uint8_t* __restrict__ repeat) {
+                                                 uint8_t* __restrict__ repeat, BySrc bs) {
   __shared__ int32_t J[T];
   __shared__ uint8_t on[T];
   const int tid = threadIdx.x;
@@ -429,11 +459,315 @@ __global__ __launch_bounds__(T) void k_rept_mark(int n, const int32_t* __restric
     }
   }
   __syncthreads();
-  if (g < n) repeat[g] = (f & SDX_RT_RB) ? ((on[tid] && !(f & SDX_RT_SREP)) ? 0 : 1) : 0;
+  if (g < n) {
+    const uint8_t r = (f & SDX_RT_RB) ? ((on[tid] && !(f & SDX_RT_SREP)) ? 0 : 1) : 0;
+    if constexpr (BS) {
+      const uint32_t line = (uint32_t)bs.perm[g];  // a permutation of [0, n): every entry is written
+      if (line < (uint32_t)n) repeat[line] = r;
+    } else {
+      repeat[g] = r;
+    }
+  }
 }
 
 }  // namespace sdxt
+
+// ---- sdx_mark_repeats_by_source: one (K, T) per source id ---------------------------
+// The lines are sorted by source id, stable, so that every source's lines stand together in stream
+// order; the timed passes above then run over positions with BS = true: a source's first result-bearing
+// line takes its predecessor from the source's own slot and is always a segment head.  Without times
+// every time is 0 and W = 0: no gap ever exceeds the window, which is the untimed definition.
+//   k_rep_keys     keys by line, as above
+//   k_reps_ids     sort key = the id (an id outside [0, S) sorts as S - 1 and its line loses its key);
+//                  the run table is cleared
+//   k_reps_hist, k_reps_scan, k_reps_scatter   one 8-bit LSD radix pass (two for S > 256) over tiles of
+//                  256 lines: digit counts per tile, their prefix over the tiles (a wave per digit), the
+//                  stable scatter.  No look-back, no global atomics (the scheme of sdx_group.hip's sort).
+//   k_reps_gather  keys, times and ids by position; every source's run [lo, hi); the tiles' last
+//                  result-bearing positions
+//   k_rep_tiles, k_rept_heads<1>, k_rep_tiles, k_rept_seg, k_rept_succ<1>, k_rept_chain<1>
+//   k_rept_mark<1> writes the mask back in line order
+//   k_reps_state   a wave per source: K from the run's last result-bearing line, T from its last head's
+//                  orbit end, the payload copied by the wave; the source's entry of the compact table
+namespace sdxs {
+using sdxt::BySrc;
+
+__global__ __launch_bounds__(T) void k_reps_ids(int n, int S, const int32_t* __restrict__ source,
+                                                uint32_t* __restrict__ skey, int32_t* __restrict__ run_lo,
+                                                int32_t* __restrict__ run_hi) {
+  const int g = blockIdx.x * T + threadIdx.x;
+  if (g < n) {
+    const uint32_t s = (uint32_t)source[g];
+    skey[g] = s < (uint32_t)S ? s : (uint32_t)S - 1u;
+  }
+  if (g < S) run_lo[g] = run_hi[g] = 0;
+}
+
+__global__ __launch_bounds__(T) void k_reps_hist(const uint32_t* __restrict__ kin, int n, int nt, int d,
+                                                 uint32_t* __restrict__ hist) {
+  __shared__ uint32_t c[256];
+  const int g = blockIdx.x * T + threadIdx.x;
+  c[threadIdx.x] = 0;
+  __syncthreads();
+  if (g < n) atomicAdd(&c[(kin[g] >> (8 * d)) & 255u], 1u);  // LDS
+  __syncthreads();
+  hist[(size_t)threadIdx.x * nt + blockIdx.x] = c[threadIdx.x];
+}
+
+// each digit's row: exclusive prefix over the tiles (one wave per row); tot[digit] = the row's total
+__global__ __launch_bounds__(T) void k_reps_scan(uint32_t* __restrict__ hist, int nt, uint32_t* __restrict__ tot) {
+  const int row = blockIdx.x * WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  uint32_t* h = hist + (size_t)row * nt;
+  uint32_t run = 0;
+  for (int b0 = 0; b0 < nt; b0 += 64) {
+    const int x = b0 + lane;
+    const uint32_t v = x < nt ? h[x] : 0u;
+    uint32_t incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t y = __shfl_up(incl, o);
+      if (lane >= o) incl += y;
+    }
+    if (x < nt) h[x] = run + incl - v;
+    run += __shfl(incl, 63);
+  }
+  if (lane == 0) tot[row] = run;
+}
+
+// a tile's lines go, in order, to (prefix of the digit totals) + (the tile's row offset) + (rank in the tile)
+__global__ __launch_bounds__(T) void k_reps_scatter(const uint32_t* __restrict__ kin, const int32_t* __restrict__ vin,
+                                                    int n, int nt, int d, const uint32_t* __restrict__ hist,
+                                                    const uint32_t* __restrict__ tot, uint32_t* __restrict__ kout,
+                                                    int32_t* __restrict__ vout) {
+  __shared__ uint32_t run[256];
+  __shared__ uint32_t wc[WAVES][256];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = blockIdx.x * T + tid;
+  const uint32_t t = tot[tid];
+  run[tid] = t;
+#pragma unroll
+  for (int w = 0; w < WAVES; ++w) wc[w][tid] = 0;
+  __syncthreads();
+  for (int o = 1; o < 256; o <<= 1) {  // inclusive scan of the digit totals
+    const uint32_t y = tid >= o ? run[tid - o] : 0u;
+    __syncthreads();
+    run[tid] += y;
+    __syncthreads();
+  }
+  const uint32_t base = run[tid] - t + hist[(size_t)tid * nt + blockIdx.x];
+  __syncthreads();
+  run[tid] = base;
+  const bool valid = g < n;
+  const uint32_t k = valid ? kin[g] : 0u;
+  const uint32_t dig = (k >> (8 * d)) & 255u;
+  uint64_t peers = __ballot(valid);  // the wave's lanes with this lane's digit
+#pragma unroll
+  for (int b = 0; b < 8; ++b) {
+    const uint64_t bal = __ballot((dig >> b) & 1u);
+    peers &= ((dig >> b) & 1u) ? bal : ~bal;
+  }
+  if (valid && lane == __ffsll((unsigned long long)peers) - 1) wc[wave][dig] = (uint32_t)__popcll(peers);
+  __syncthreads();
+  if (valid) {
+    uint32_t pos = run[dig] + (uint32_t)__popcll(lane ? peers & (~0ull >> (64 - lane)) : 0ull);
+    for (int w = 0; w < wave; ++w) pos += wc[w][dig];
+    if (pos < (uint32_t)n) {  // always, the counts sum to n
+      kout[pos] = k;
+      vout[pos] = vin ? vin[g] : g;
+    }
+  }
+}
+
+__global__ __launch_bounds__(T) void k_reps_gather(int n, int S, const int32_t* __restrict__ perm,
+                                                   const uint32_t* __restrict__ psrc, const int32_t* __restrict__ source,
+                                                   const sdx_repeat_key* __restrict__ lkeys,
+                                                   const int64_t* __restrict__ times, sdx_repeat_key* __restrict__ keys,
+                                                   int64_t* __restrict__ ptimes, int32_t* __restrict__ run_lo,
+                                                   int32_t* __restrict__ run_hi, int32_t* __restrict__ tile_last) {
+  __shared__ int32_t wlast[WAVES];
+  const int g = blockIdx.x * T + threadIdx.x;
+  bool have = false;
+  if (g < n) {
+    const uint32_t line = (uint32_t)perm[g];
+    uint4 v = make_uint4(SDX_REPEAT_NONE, 0, 0, 0);
+    int64_t t = 0;
+    if (line < (uint32_t)n) {
+      if ((uint32_t)source[line] < (uint32_t)S) v = *reinterpret_cast<const uint4*>(lkeys + line);
+      if (times) t = times[line];
+    }
+    *reinterpret_cast<uint4*>(keys + g) = v;
+    ptimes[g] = t;
+    have = v.x != SDX_REPEAT_NONE;
+    const uint32_t s = psrc[g];
+    if (s < (uint32_t)S) {
+      if (g == 0 || psrc[g - 1] != s) run_lo[s] = g;
+      if (g == n - 1 || psrc[g + 1] != s) run_hi[s] = g + 1;
+    }
+  }
+  const uint64_t m = __ballot(have);
+  if ((threadIdx.x & 63) == 0) wlast[threadIdx.x >> 6] = m ? (int)(g - (threadIdx.x & 63) + last_bit(m)) : -1;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int last = -1;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) last = max(last, wlast[w]);
+    tile_last[blockIdx.x] = last;
+  }
+}
+
+__global__ __launch_bounds__(T) void k_reps_state(Kinds in, int n, int nt, int S, const sdx_repeat_key* __restrict__ keys,
+                                                  const int32_t* __restrict__ run_lo, const int32_t* __restrict__ run_hi,
+                                                  const int32_t* __restrict__ ipred, const int32_t* __restrict__ seg,
+                                                  const int32_t* __restrict__ exitv, const int32_t* __restrict__ lastv,
+                                                  const int64_t* __restrict__ te, const uint8_t* __restrict__ flags,
+                                                  const int32_t* __restrict__ perm, uint8_t* __restrict__ state,
+                                                  sdx_repeat_source_entry* __restrict__ table) {
+  const int s = blockIdx.x * WAVES + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (s >= S) return;
+  uint8_t* slot = state + (size_t)s * SDX_REPEAT_TIMED_STATE_SIZE;
+  sdx_repeat_timed_state_hdr h = *reinterpret_cast<const sdx_repeat_timed_state_hdr*>(slot);
+  const int lo = run_lo[s], hi = run_hi[s];
+  int last = -1;
+  if (lo >= 0 && lo < hi && hi <= n) {
+    last = ipred[hi - 1];
+    if (last < lo || last >= hi) last = -1;
+  }
+  int line = -1;
+  if (last >= 0) {  // the source has a result-bearing line in this chunk
+    const uint4 v = *reinterpret_cast<const uint4*>(keys + last);
+    h.valid = 1;
+    h.kind = v.x;
+    h.proto = v.y;
+    h.len = v.z;
+    const int hd = seg[hi - 1];  // the run's last head: its first result-bearing line is one
+    if (hd >= lo && hd < hi) {
+      int x = hd;  // an orbit that leaves its tile is followed from tile to tile, as k_rept_chain does
+      for (int it = 0; it < nt; ++it) {
+        const int e = exitv[x];
+        if (e < 0 || e >= n) break;
+        x = e;
+      }
+      const int l = lastv[x];
+      if (l >= 0 && l < n && !(l == hd && (flags[hd] & SDX_RT_SREP))) h.t = te[l];
+    }
+    const uint32_t pl = (uint32_t)perm[last];
+    line = pl < (uint32_t)n ? (int)pl : -1;
+    if (v.x <= (uint32_t)SDX_KIND_MN && in.k[v.x].heap) {
+      const uint8_t* src = in.k[v.x].heap + v.w;
+      uint8_t* dst = slot + sizeof(sdx_repeat_timed_state_hdr);
+      for (uint32_t i = lane; i < v.z; i += 64) dst[i] = src[i];
+    }
+    if (lane == 0) *reinterpret_cast<sdx_repeat_timed_state_hdr*>(slot) = h;
+  }
+  if (lane == 0) table[s] = sdx_repeat_source_entry{h.valid, h.kind, h.proto, h.len, h.t, line, 0};
+}
+
+}  // namespace sdxs
 }  // namespace sdxr
+
+extern "C" size_t sdx_repeat_sources_state_bytes(int32_t n_sources) { return sdx_repeat_sources_state_size(n_sources); }
+extern "C" size_t sdx_repeat_sources_scratch_bytes(int32_t n, int32_t n_sources) {
+  return sdx_repeat_sources_scratch_size(n, n_sources);
+}
+
+extern "C" int sdx_mark_repeats_by_source(const sdx_bank* bank, const sdx_json_in* kinds, int k, int32_t n,
+                                          const int32_t* source_dev, int32_t n_sources, const int64_t* times_dev,
+                                          int64_t window_us, uint8_t* repeat_dev, void* scratch_dev, void* state_dev,
+                                          void* hip_stream) {
+  namespace sdxt = sdxr::sdxt;
+  namespace sdxs = sdxr::sdxs;
+  (void)bank;
+  if (!kinds || k < 1 || k > 4) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: 1 to 4 kinds");
+  if (n < 0) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: n < 0");
+  if (!sdx_rs_sources_ok(n_sources))
+    return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: n_sources must be 1 .. SDX_REPEAT_SOURCES_MAX");
+  if (times_dev && window_us < 0) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: window_us < 0");
+  if (!source_dev || !repeat_dev || !scratch_dev || !state_dev)
+    return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: null buffer");
+  if ((((uintptr_t)scratch_dev | (uintptr_t)state_dev) & 15) || ((uintptr_t)times_dev & 7) || ((uintptr_t)source_dev & 3))
+    return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: scratch_dev and state_dev must be 16-byte, "
+                                      "times_dev 8-byte, source_dev 4-byte aligned");
+  sdxr::Kinds in{};
+  for (int i = 0; i < k; ++i) {
+    const sdx_json_in& j = kinds[i];
+    if (j.kind < SDX_KIND_MU || j.kind > SDX_KIND_MN)
+      return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: bad kind");
+    if (in.k[j.kind].desc) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: a kind given twice");
+    if (!j.desc_dev || !j.rec_dev || !j.heap_dev)
+      return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: null buffer");
+    if (j.n != n) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: every kind's n must be the chunk's n");
+    in.k[j.kind] = sdxr::KindIn{j.desc_dev, j.rec_dev, j.heap_dev};
+  }
+  if (n == 0) return SDX_OK;
+  const int S = n_sources;
+  const int64_t window = times_dev ? window_us : 0;
+  uint8_t* s = static_cast<uint8_t*>(scratch_dev);
+  auto part = [&](int p) { return s + sdx_rs_off(n, S, p); };
+  int32_t* head = reinterpret_cast<int32_t*>(part(SDX_RS_HEAD));
+  sdx_repeat_source_entry* table = reinterpret_cast<sdx_repeat_source_entry*>(part(SDX_RS_TABLE));
+  int32_t* run_lo = reinterpret_cast<int32_t*>(part(SDX_RS_RUN_LO));
+  int32_t* run_hi = reinterpret_cast<int32_t*>(part(SDX_RS_RUN_HI));
+  sdx_repeat_key* lkeys = reinterpret_cast<sdx_repeat_key*>(part(SDX_RS_LKEYS));
+  sdx_repeat_key* keys = reinterpret_cast<sdx_repeat_key*>(part(SDX_RS_KEYS));
+  int64_t* te = reinterpret_cast<int64_t*>(part(SDX_RS_TE));
+  int64_t* ptimes = reinterpret_cast<int64_t*>(part(SDX_RS_PTIMES));
+  int32_t* seg = reinterpret_cast<int32_t*>(part(SDX_RS_SEG));
+  int32_t* succ = reinterpret_cast<int32_t*>(part(SDX_RS_SUCC));
+  int32_t* exitv = reinterpret_cast<int32_t*>(part(SDX_RS_EXIT));
+  int32_t* lastv = reinterpret_cast<int32_t*>(part(SDX_RS_LAST));
+  int32_t* ipred = reinterpret_cast<int32_t*>(part(SDX_RS_IPRED));
+  int32_t* perm = reinterpret_cast<int32_t*>(part(SDX_RS_PERM));
+  uint32_t* k0 = reinterpret_cast<uint32_t*>(part(SDX_RS_K0));
+  uint32_t* k1 = reinterpret_cast<uint32_t*>(part(SDX_RS_K1));
+  int32_t* v0 = reinterpret_cast<int32_t*>(part(SDX_RS_V0));
+  const int nt = (int)sdx_repeat_tiles(n);
+  int32_t* tiles = reinterpret_cast<int32_t*>(part(SDX_RS_TILES));
+  int32_t *tile_last = tiles, *tile_prev = tiles + nt, *tile_head = tiles + 2 * nt, *tile_prevhead = tiles + 3 * nt,
+          *tile_arr = tiles + 4 * nt, *tile_spare = tiles + 5 * nt;
+  uint32_t* hist = reinterpret_cast<uint32_t*>(part(SDX_RS_HIST));
+  uint32_t* tot = reinterpret_cast<uint32_t*>(part(SDX_RS_TOT));
+  uint8_t* flags = part(SDX_RS_FLAGS);
+  uint8_t* state = static_cast<uint8_t*>(state_dev);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const dim3 grid(nt), blk(sdxr::T);
+  hipLaunchKernelGGL(sdxr::k_rep_keys, grid, blk, 0, st, in, (int)n, lkeys, tile_spare);
+  const int gi = ((n > S ? n : S) + sdxr::T - 1) / sdxr::T;
+  hipLaunchKernelGGL(sdxs::k_reps_ids, dim3(gi), blk, 0, st, (int)n, S, source_dev, k0, run_lo, run_hi);
+  const int passes = sdx_rs_passes(S);
+  uint32_t* psrc = k1;
+  for (int d = 0; d < passes; ++d) {  // (k0, line) -> (k1, v0 or perm) -> (k0, perm)
+    uint32_t *kin = d ? k1 : k0, *kout = d ? k0 : k1;
+    hipLaunchKernelGGL(sdxs::k_reps_hist, grid, blk, 0, st, (const uint32_t*)kin, (int)n, nt, d, hist);
+    hipLaunchKernelGGL(sdxs::k_reps_scan, dim3(256 / sdxr::WAVES), blk, 0, st, hist, nt, tot);
+    hipLaunchKernelGGL(sdxs::k_reps_scatter, grid, blk, 0, st, (const uint32_t*)kin, (const int32_t*)(d ? v0 : nullptr),
+                       (int)n, nt, d, (const uint32_t*)hist, (const uint32_t*)tot, kout, d == passes - 1 ? perm : v0);
+    psrc = kout;
+  }
+  hipLaunchKernelGGL(sdxs::k_reps_gather, grid, blk, 0, st, (int)n, S, (const int32_t*)perm, (const uint32_t*)psrc,
+                     source_dev, (const sdx_repeat_key*)lkeys, times_dev, keys, ptimes, run_lo, run_hi, tile_last);
+  const sdxt::BySrc bs{psrc, perm, ipred, S};
+  hipLaunchKernelGGL(sdxr::k_rep_tiles, dim3(1), dim3(sdxr::ST), 0, st, (const int32_t*)tile_last, nt, tile_prev, head);
+  hipLaunchKernelGGL(sdxt::k_rept_heads<true>, grid, blk, 0, st, in, (int)n, (const sdx_repeat_key*)keys,
+                     (const int32_t*)tile_prev, (const int64_t*)ptimes, window, (const uint8_t*)state, te, flags, tile_head,
+                     tile_arr, bs);
+  hipLaunchKernelGGL(sdxr::k_rep_tiles, dim3(1), dim3(sdxr::ST), 0, st, (const int32_t*)tile_head, nt, tile_prevhead,
+                     head + 1);
+  hipLaunchKernelGGL(sdxt::k_rept_seg, grid, blk, 0, st, (int)n, (const uint8_t*)flags, (const int32_t*)tile_prevhead, seg);
+  hipLaunchKernelGGL(sdxt::k_rept_succ<true>, grid, blk, 0, st, (int)n, (const int64_t*)te, (const int32_t*)seg,
+                     (const uint8_t*)flags, window, (const uint8_t*)state, succ, exitv, lastv, bs);
+  hipLaunchKernelGGL(sdxt::k_rept_chain<true>, dim3(1), dim3(sdxr::ST), 0, st, in, (int)n, nt, (const sdx_repeat_key*)keys,
+                     (const int32_t*)head, (const int32_t*)tile_head, (const int32_t*)exitv, (const int32_t*)lastv,
+                     (const int64_t*)te, (const uint8_t*)flags, tile_arr, state);
+  hipLaunchKernelGGL(sdxt::k_rept_mark<true>, grid, blk, 0, st, (int)n, (const int32_t*)succ, (const uint8_t*)flags,
+                     (const int32_t*)tile_arr, repeat_dev, bs);
+  hipLaunchKernelGGL(sdxs::k_reps_state, dim3((S + sdxr::WAVES - 1) / sdxr::WAVES), blk, 0, st, in, (int)n, nt, S,
+                     (const sdx_repeat_key*)keys, (const int32_t*)run_lo, (const int32_t*)run_hi, (const int32_t*)ipred,
+                     (const int32_t*)seg, (const int32_t*)exitv, (const int32_t*)lastv, (const int64_t*)te,
+                     (const uint8_t*)flags, (const int32_t*)perm, state, table);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return sdx::set_error(SDX_EHIP, std::string("sdx_mark_repeats_by_source: ") + hipGetErrorString(e));
+  return SDX_OK;
+}
 
 extern "C" size_t sdx_repeat_timed_state_bytes(void) { return sdx_repeat_timed_state_size(); }
 extern "C" size_t sdx_repeat_timed_scratch_bytes(int32_t n) { return sdx_repeat_timed_scratch_size(n); }
@@ -482,20 +816,20 @@ extern "C" int sdx_mark_repeats_timed(const sdx_bank* bank, const sdx_json_in* k
   hipStream_t st = (hipStream_t)hip_stream;
   hipLaunchKernelGGL(sdxr::k_rep_keys, dim3(nt), dim3(sdxr::T), 0, st, in, (int)n, keys, tile_last);
   hipLaunchKernelGGL(sdxr::k_rep_tiles, dim3(1), dim3(sdxr::ST), 0, st, (const int32_t*)tile_last, nt, tile_prev, head);
-  hipLaunchKernelGGL(sdxt::k_rept_heads, dim3(nt), dim3(sdxr::T), 0, st, in, (int)n, (const sdx_repeat_key*)keys,
+  hipLaunchKernelGGL(sdxt::k_rept_heads<false>, dim3(nt), dim3(sdxr::T), 0, st, in, (int)n, (const sdx_repeat_key*)keys,
                      (const int32_t*)tile_prev, times_dev, window_us, (const uint8_t*)state, te, flags, tile_head,
-                     tile_arr);
+                     tile_arr, sdxt::BySrc{});
   hipLaunchKernelGGL(sdxr::k_rep_tiles, dim3(1), dim3(sdxr::ST), 0, st, (const int32_t*)tile_head, nt, tile_prevhead,
                      head + 1);
   hipLaunchKernelGGL(sdxt::k_rept_seg, dim3(nt), dim3(sdxr::T), 0, st, (int)n, (const uint8_t*)flags,
                      (const int32_t*)tile_prevhead, seg);
-  hipLaunchKernelGGL(sdxt::k_rept_succ, dim3(nt), dim3(sdxr::T), 0, st, (int)n, (const int64_t*)te, (const int32_t*)seg,
-                     (const uint8_t*)flags, window_us, (const uint8_t*)state, succ, exitv, lastv);
-  hipLaunchKernelGGL(sdxt::k_rept_chain, dim3(1), dim3(sdxr::ST), 0, st, in, (int)n, nt, (const sdx_repeat_key*)keys,
+  hipLaunchKernelGGL(sdxt::k_rept_succ<false>, dim3(nt), dim3(sdxr::T), 0, st, (int)n, (const int64_t*)te, (const int32_t*)seg,
+                     (const uint8_t*)flags, window_us, (const uint8_t*)state, succ, exitv, lastv, sdxt::BySrc{});
+  hipLaunchKernelGGL(sdxt::k_rept_chain<false>, dim3(1), dim3(sdxr::ST), 0, st, in, (int)n, nt, (const sdx_repeat_key*)keys,
                      (const int32_t*)head, (const int32_t*)tile_head, (const int32_t*)exitv, (const int32_t*)lastv,
                      (const int64_t*)te, (const uint8_t*)flags, tile_arr, state);
-  hipLaunchKernelGGL(sdxt::k_rept_mark, dim3(nt), dim3(sdxr::T), 0, st, (int)n, (const int32_t*)succ,
-                     (const uint8_t*)flags, (const int32_t*)tile_arr, repeat_dev);
+  hipLaunchKernelGGL(sdxt::k_rept_mark<false>, dim3(nt), dim3(sdxr::T), 0, st, (int)n, (const int32_t*)succ,
+                     (const uint8_t*)flags, (const int32_t*)tile_arr, repeat_dev, sdxt::BySrc{});
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return sdx::set_error(SDX_EHIP, std::string("sdx_mark_repeats_timed: ") + hipGetErrorString(e));
   return SDX_OK;

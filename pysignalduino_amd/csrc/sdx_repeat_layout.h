@@ -1,8 +1,8 @@
 // sdx_repeat_layout.h -- sizes and offsets of sdx_mark_repeats' two caller-owned buffers, and of
-// sdx_mark_repeats_timed's two (further down), host + device.
+// sdx_mark_repeats_timed's and sdx_mark_repeats_by_source's two each (further down), host + device.
 // Plain C++ without any HIP type, so that a stand-alone host program can include it
-// (tools/repeat_layout_check.cpp and tools/repeat_timed_layout_check.cpp run these functions under the
-// address / UB sanitizers).
+// (tools/repeat_layout_check.cpp, tools/repeat_timed_layout_check.cpp and
+// tools/repeat_sources_layout_check.cpp run these functions under the address / UB sanitizers).
 //
 //   state    [ sdx_repeat_state_hdr | payload bytes, room for SDX_REPEAT_PAYLOAD_MAX ]
 //   scratch  [ head: 4 x int32, [0] = the chunk's last result-bearing line or -1
@@ -72,9 +72,9 @@ typedef struct {
   int64_t t;       /* T, microseconds */
 } sdx_repeat_timed_state_hdr; /* 24 bytes, the payload bytes follow */
 
-static inline size_t sdx_repeat_timed_state_size(void) {
-  return (sizeof(sdx_repeat_timed_state_hdr) + (size_t)SDX_REPEAT_PAYLOAD_MAX + 15) & ~(size_t)15;
-}
+/* a macro, so that device code can use it too (the slots of sdx_mark_repeats_by_source) */
+#define SDX_REPEAT_TIMED_STATE_SIZE ((sizeof(sdx_repeat_timed_state_hdr) + (size_t)SDX_REPEAT_PAYLOAD_MAX + 15) & ~(size_t)15)
+static inline size_t sdx_repeat_timed_state_size(void) { return SDX_REPEAT_TIMED_STATE_SIZE; }
 
 static inline size_t sdx_rt_lines(int64_t n) { return (size_t)(n > 0 ? n : 0); }
 static inline size_t sdx_rt_keys_off(void) { return 16; }
@@ -91,4 +91,80 @@ static inline size_t sdx_rt_flags_off(int64_t n) { return sdx_rt_tile_off(n, 5);
 static inline size_t sdx_repeat_timed_scratch_size(int64_t n) {
   return (sdx_rt_flags_off(n) + sdx_rt_lines(n) + 15) & ~(size_t)15;
 }
+
+/* ---- sdx_mark_repeats_by_source: one (K, T) per source id, buffers of its own --------------------
+ *   state    n_sources slots of sdx_repeat_timed_state_size() bytes, each with the timed state's layout;
+ *            slot s carries source s
+ *   scratch  the parts below in this order, each rounded up to 16 bytes.  "position" = a line's place
+ *            after the stable sort by source id, so that every source's lines are contiguous and in
+ *            stream order; the timed pass's arrays are indexed by position here */
+#define SDX_REPEAT_SOURCES_MAX 4096
+
+typedef struct {
+  uint32_t valid;  /* the slot's header after this chunk ... */
+  uint32_t kind, proto, len;
+  int64_t t;       /* ... and its T */
+  int32_t last;    /* the source's last result-bearing line in this chunk (line index), -1 = none */
+  int32_t pad;
+} sdx_repeat_source_entry; /* 32 bytes */
+
+enum {
+  SDX_RS_HEAD,    /* 4 x int32: [0] = the last result-bearing position, [1] = the last segment head */
+  SDX_RS_TABLE,   /* sdx_repeat_source_entry[S]: what the host reads back, one copy per chunk */
+  SDX_RS_RUN_LO,  /* int32[S]  first position of the source's lines ... */
+  SDX_RS_RUN_HI,  /* int32[S]  ... and the position behind its last (lo == hi: absent) */
+  SDX_RS_LKEYS,   /* sdx_repeat_key[n] by line */
+  SDX_RS_KEYS,    /* sdx_repeat_key[n] by position */
+  SDX_RS_TE,      /* int64[n] as the timed pass's */
+  SDX_RS_PTIMES,  /* int64[n] the lines' times by position (0 without times) */
+  SDX_RS_SEG,     /* int32[n] */
+  SDX_RS_SUCC,    /* int32[n] */
+  SDX_RS_EXIT,    /* int32[n] */
+  SDX_RS_LAST,    /* int32[n] */
+  SDX_RS_IPRED,   /* int32[n] the last result-bearing position at or in front of the position, -1 = none */
+  SDX_RS_PERM,    /* int32[n] position -> line */
+  SDX_RS_K0,      /* uint32[n] sort keys (the clamped ids), two copies, and one spare copy of the values */
+  SDX_RS_K1,
+  SDX_RS_V0,
+  SDX_RS_TILES,   /* int32[6 * tiles]: tile_last, tile_prev, tile_head, tile_prevhead, tile_arr, spare */
+  SDX_RS_HIST,    /* uint32[256 * tiles]: hist[digit * tiles + tile] */
+  SDX_RS_TOT,     /* uint32[256] */
+  SDX_RS_FLAGS,   /* uint8[n] SDX_RT_* */
+  SDX_RS_END
+};
+
+static inline int sdx_rs_sources_ok(int64_t n_sources) { return n_sources >= 1 && n_sources <= SDX_REPEAT_SOURCES_MAX; }
+
+static inline size_t sdx_rs_part_bytes(int64_t n, int64_t n_sources, int part) {
+  const size_t L = sdx_rt_lines(n), S = sdx_rs_sources_ok(n_sources) ? (size_t)n_sources : 0;
+  const size_t tiles = (size_t)sdx_repeat_tiles(n);
+  switch (part) {
+    case SDX_RS_HEAD: return 16;
+    case SDX_RS_TABLE: return sizeof(sdx_repeat_source_entry) * S;
+    case SDX_RS_RUN_LO: case SDX_RS_RUN_HI: return sizeof(int32_t) * S;
+    case SDX_RS_LKEYS: case SDX_RS_KEYS: return sizeof(sdx_repeat_key) * L;
+    case SDX_RS_TE: case SDX_RS_PTIMES: return sizeof(int64_t) * L;
+    case SDX_RS_SEG: case SDX_RS_SUCC: case SDX_RS_EXIT: case SDX_RS_LAST: case SDX_RS_IPRED: case SDX_RS_PERM:
+    case SDX_RS_K0: case SDX_RS_K1: case SDX_RS_V0: return sizeof(int32_t) * L;
+    case SDX_RS_TILES: return sizeof(int32_t) * 6 * tiles;
+    case SDX_RS_HIST: return sizeof(uint32_t) * 256 * tiles;
+    case SDX_RS_TOT: return sizeof(uint32_t) * 256;
+    case SDX_RS_FLAGS: return L;
+    default: return 0;
+  }
+}
+/* offset of a part; sdx_rs_off(n, S, SDX_RS_END) = the scratch buffer's size */
+static inline size_t sdx_rs_off(int64_t n, int64_t n_sources, int part) {
+  size_t off = 0;
+  for (int p = 0; p < part && p < SDX_RS_END; ++p) off += (sdx_rs_part_bytes(n, n_sources, p) + 15) & ~(size_t)15;
+  return off;
+}
+static inline size_t sdx_repeat_sources_scratch_size(int64_t n, int64_t n_sources) {
+  return sdx_rs_sources_ok(n_sources) ? sdx_rs_off(n, n_sources, SDX_RS_END) : 0;
+}
+static inline size_t sdx_repeat_sources_state_size(int64_t n_sources) {
+  return sdx_rs_sources_ok(n_sources) ? (size_t)n_sources * sdx_repeat_timed_state_size() : 0;
+}
+/* radix passes of 8 bits over the ids 0 .. S - 1 */
+static inline int sdx_rs_passes(int64_t n_sources) { return n_sources > 256 ? 2 : 1; }
 #endif

@@ -309,9 +309,10 @@ class SignalParser:
         return out
 
     @staticmethod
-    def _window_args(collapse: bool, times, repeat_window, n: int):
+    def _window_args(collapse: bool, times, repeat_window, n: int, sources=None):
         """-> (times as int64[n], W in microseconds), (None, None) without a window; ValueError for a window
-        without collapse_repeats or without times, and for times that decrease (repeats.py)."""
+        without collapse_repeats or without times, and for times that decrease (repeats.py) -- with
+        ``sources`` (repeats.check_sources' array) within a source."""
         if repeat_window is None:
             if times is not None and len(times) != n:
                 raise ValueError(f"times: {len(times)} times for {n} lines")
@@ -320,29 +321,43 @@ class SignalParser:
         if not collapse:
             raise ValueError("repeat_window needs collapse_repeats=True")
         w = window_to_us(repeat_window)
-        return check_times(times, n), w
+        return check_times(times, n, sources=sources), w
+
+    @staticmethod
+    def _source_args(collapse: bool, sources, n: int):
+        """-> the lines' source ids as int32[n], None without ``sources``; ValueError without
+        collapse_repeats and for ids that are no integers inside [0, 4096) (repeats.py)."""
+        if sources is None:
+            return None
+        if not collapse:
+            raise ValueError("sources needs collapse_repeats=True")
+        from .repeats import check_sources
+        return check_sources(sources, n)
 
     def parse_lines(self, lines: Sequence[Union[str, bytes]], collapse_repeats: bool = False, times=None,
-                    repeat_window: Optional[float] = None) -> List[Union[List[DecodedMessage], Exception]]:
+                    repeat_window: Optional[float] = None, sources=None) -> List[Union[List[DecodedMessage], Exception]]:
         """Batch form of parse_line: one upload, one parse launch, one launch per demodulation
         variant, one read-back.  Returns one DecodedMessage list per line (or the ContractError
         for a line outside the device contract).  ``collapse_repeats``: a line that repeats the
         previous result-bearing line's (kind, protocol, payload) gives [] (repeats.py; the mask is
         left in ``last_repeat_mask``).  ``repeat_window`` (seconds) with ``times`` (one arrival time in
         integer microseconds per line, non-decreasing): a run also ends once its last published line
-        is more than the window old, as FHEM dispatches (repeats.py)."""
-        times, w = self._window_args(collapse_repeats, times, repeat_window, len(lines))
+        is more than the window old, as FHEM dispatches (repeats.py).  ``sources`` (one integer id per
+        line, the receiver it came from): every source's lines are a stream of their own -- runs, keys and
+        the window's anchor per source, the times non-decreasing within a source."""
+        sources = self._source_args(collapse_repeats, sources, len(lines))
+        times, w = self._window_args(collapse_repeats, times, repeat_window, len(lines), sources)
         if len(lines) == 0:
             return self._collapsed([], collapse_repeats)
         data, offsets, bad = pack_lines(lines)
         return self._collapsed(self._objects(lines, LineBatch(self.protocols._ensure(), data, offsets), offsets, bad,
-                                             len(data)), collapse_repeats, times, w)
+                                             len(data)), collapse_repeats, times, w, sources)
 
-    def _collapsed(self, out: list, collapse: bool, times=None, window_us=None) -> list:
+    def _collapsed(self, out: list, collapse: bool, times=None, window_us=None, sources=None) -> list:
         """Object output: every payload is on the host already, so the repeats are marked there."""
         if collapse:
             from .repeats import collapse_objects
-            self.last_repeat_mask = collapse_objects(out, times, window_us)
+            self.last_repeat_mask = collapse_objects(out, times, window_us, sources=sources)
         return out
 
     def _objects(self, lines, lb: LineBatch, offsets: np.ndarray, bad: dict, nbytes: int):
@@ -531,18 +546,22 @@ class SignalParser:
 
     # ------------------------------------------------------------------------------------------
     def stream(self, chunk_lines: int = 250_000, chunk_bytes: Optional[int] = None, output: str = "json",
-               lag: int = 3, collapse_repeats: bool = False, repeat_window: Optional[float] = None):
+               lag: int = 3, collapse_repeats: bool = False, repeat_window: Optional[float] = None,
+               repeat_sources: Optional[int] = None):
         """A pipelined LineStream over this parser (pysignalduino_amd/stream.py): chunks of raw lines
         in, the controller's JSON texts (or the wire form) out, the PCIe copies, parse, demodulation
         and serialisation of successive chunks overlapping; the same per-line results as
-        parse_lines_json / parse_lines."""
+        parse_lines_json / parse_lines.  ``repeat_sources``: the stream merges that many receivers, every
+        submit names its lines' source ids and repeat suppression runs per source (stream.py)."""
         from .stream import LineStream
+        kw = {} if repeat_window is None else {"repeat_window": repeat_window}
+        if repeat_sources is not None:
+            kw["repeat_sources"] = repeat_sources
         return LineStream(self, chunk_lines=chunk_lines, chunk_bytes=chunk_bytes, output=output, lag=lag,
-                          collapse_repeats=collapse_repeats, **({} if repeat_window is None else
-                                                                {"repeat_window": repeat_window}))
+                          collapse_repeats=collapse_repeats, **kw)
 
     def parse_lines_json(self, lines: Sequence[Union[str, bytes]], collapse_repeats: bool = False, times=None,
-                         repeat_window: Optional[float] = None) -> List[Union[Optional[str], Exception]]:
+                         repeat_window: Optional[float] = None, sources=None) -> List[Union[Optional[str], Exception]]:
         """Per line, the MQTT message text the reference controller publishes for it:
         ``MqttPublisher._message_to_json(parse_line(line)[0])`` (signalduino/controller.py:254-257,
         mqtt.py:227-245), or None when the line decodes to nothing -- parse, demodulation and JSON
@@ -551,18 +570,22 @@ class SignalParser:
         payload) gives None -- marked on the device (sdx_mark_repeats) and never serialised; the mask
         is left in ``last_repeat_mask``.  ``repeat_window`` (seconds) with ``times`` (one arrival time in
         integer microseconds per line, non-decreasing; checked before anything is launched): a run also
-        ends once its last published line is more than the window old (sdx_mark_repeats_timed)."""
-        times, w = self._window_args(collapse_repeats, times, repeat_window, len(lines))
+        ends once its last published line is more than the window old (sdx_mark_repeats_timed).
+        ``sources`` (one integer id per line, the receiver it came from; S = the largest id + 1): every
+        source's lines are a stream of their own (sdx_mark_repeats_by_source), the times non-decreasing
+        within a source."""
+        sources = self._source_args(collapse_repeats, sources, len(lines))
+        times, w = self._window_args(collapse_repeats, times, repeat_window, len(lines), sources)
         if len(lines) == 0:
             if collapse_repeats:
                 self.last_repeat_mask = np.zeros(0, np.uint8)
             return []
         data, offsets, bad = pack_lines(lines)
         return self._texts(lines, LineBatch(self.protocols._ensure(), data, offsets), bad, len(data), collapse_repeats,
-                           times, w)
+                           times, w, sources)
 
     def _texts(self, lines, lb: LineBatch, bad: dict, nbytes: int, collapse: bool = False, times=None,
-               window_us: Optional[int] = None):
+               window_us: Optional[int] = None, sources=None):
         """parse_lines_json from the uploaded batch on (``lines`` and ``nbytes`` as in _objects)."""
         n = len(lines)
         eng = self.protocols._ensure()
@@ -633,7 +656,17 @@ class SignalParser:
                 else:
                     raise RuntimeError("result capacity overflow persists")
                 kept.append((kind, out, json_cap))
-            if kept and window_us is not None:
+            table = None
+            if kept and sources is not None:   # one (K, T) per source id
+                from .repeats import count_sources
+                S = count_sources(sources)
+                rep_dev, scratch = eng.alloc_repeat_sources(n, S)
+                eng.mark_repeats_by_source([eng.json_in(kind, out, lo, n) for kind, out, _ in kept], n,
+                                           eng.torch.from_numpy(sources).to(eng.dev), S,
+                                           None if window_us is None else eng.torch.from_numpy(times).to(eng.dev),
+                                           window_us, rep_dev, scratch, eng.alloc_repeat_state(sources=S))
+                table = eng.repeat_sources_table(scratch, S).cpu().numpy().view(runtime.REPEAT_SOURCE_ENTRY)
+            elif kept and window_us is not None:
                 rep_dev, scratch = eng.alloc_repeat_timed(n)
                 times_dev = eng.torch.from_numpy(times).to(eng.dev)
                 eng.mark_repeats_timed([eng.json_in(kind, out, lo, n) for kind, out, _ in kept], n, times_dev, window_us,
@@ -705,16 +738,20 @@ class SignalParser:
                 texts[i] = ContractError(f"line {i} is outside the device contract of the front end "
                                          f"(kind {_KIND_NAME.get(int(kinds[i]), '?')})")
         if collapse:
-            from .repeats import RepeatTracker, text_key
+            from .repeats import RepeatTracker, SourceTrackers, text_key
             fetched = {}
 
             def fetch_key(i):   # a flagged line whose run head the host does not know: the batch API
                 fetched[i] = self.parse_lines_json([lines[i]])[0]
                 return text_key(_KIND_NAME[int(kinds[i])], fetched[i]) if isinstance(fetched[i], str) else None
 
-            mask = RepeatTracker().fix_chunk(rep, has_text, lambda i: text_key(_KIND_NAME[int(kinds[i])], texts[i]),
-                                             host_keys, fetch_key=fetch_key,
-                                             **({} if window_us is None else {"times": times, "window_us": window_us}))
+            wkw = {} if window_us is None else {"times": times, "window_us": window_us}
+            dev_key_of = lambda i: text_key(_KIND_NAME[int(kinds[i])], texts[i])   # noqa: E731
+            if sources is not None:
+                mask = SourceTrackers().fix_chunk(sources, rep, has_text, dev_key_of, host_keys, fetch_key=fetch_key,
+                                                  table=table, **wkw)
+            else:
+                mask = RepeatTracker().fix_chunk(rep, has_text, dev_key_of, host_keys, fetch_key=fetch_key, **wkw)
             for i in sorted(set(np.nonzero(mask != rep)[0].tolist()) | set(host_keys)):
                 if mask[i]:
                     texts[i] = None      # a host-resolved repeat, or a repeat of a host-resolved line

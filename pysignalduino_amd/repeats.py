@@ -17,6 +17,11 @@ and T = t; K = k in both cases.  The anchor is the last published line, not the 
 ``repeat_window`` is given in seconds and becomes ``window_to_us(repeat_window)``.  Without a window
 there is no time-based expiry.
 
+A stream that merges several receivers gives every line a source id (``sources``, 0 <= id < S <= 4096): for
+each source the subsequence of lines with that id is a stream of its own by the two definitions above, with
+its own (K, T); lines of other sources neither start, break nor time out a run, and the times are
+non-decreasing within a source only (sdx_mark_repeats_by_source; :class:`SourceTrackers` on the host).
+
 The device decides this for the lines it demodulates (sdx_mark_repeats, with a window
 sdx_mark_repeats_timed; csrc/sdx_repeat.hip).  Lines the
 batch API resolves on the host (the general path, lines outside the contract, re-runs after an
@@ -66,9 +71,43 @@ def window_to_us(repeat_window) -> Optional[int]:
     return w
 
 
-def check_times(times, n: int, last: Optional[int] = None) -> np.ndarray:
+SOURCES_MAX = 4096   # SDX_REPEAT_SOURCES_MAX
+
+
+def check_sources(sources, n: int, n_sources: Optional[int] = None) -> np.ndarray:
+    """One call's or chunk's source ids as int32[n]; ValueError unless there are n integers inside
+    [0, n_sources).  ``n_sources`` None (a one-shot call): the largest id + 1, at most SOURCES_MAX."""
+    if sources is None:
+        raise ValueError("the lines' source ids are missing (sources=)")
+    s = np.asarray(sources)
+    if s.dtype.kind not in "iu" or s.ndim != 1:
+        raise ValueError("sources: one integer id per line")
+    if len(s) != n:
+        raise ValueError(f"sources: {len(s)} ids for {n} lines")
+    top = SOURCES_MAX if n_sources is None else int(n_sources)
+    if n and (int(s.min()) < 0 or int(s.max()) >= top):
+        raise ValueError(f"sources: ids must be inside [0, {top})")
+    return s.astype(np.int32, copy=False)
+
+
+def count_sources(sources: np.ndarray) -> int:
+    """S of a one-shot call: the largest id + 1."""
+    return int(sources.max()) + 1 if len(sources) else 1
+
+
+def by_source(sources: np.ndarray):
+    """-> [(source id, the indices of its lines in line order)] for the ids present, in id order."""
+    order = np.argsort(sources, kind="stable")
+    ss = sources[order]
+    cuts = np.flatnonzero(ss[1:] != ss[:-1]) + 1
+    return [(int(sources[g[0]]), g) for g in np.split(order, cuts)] if len(order) else []
+
+
+def check_times(times, n: int, last=None, sources: Optional[np.ndarray] = None) -> np.ndarray:
     """One call's or chunk's arrival times as int64[n]; ValueError unless there are n of them, they do not
-    decrease, and the first is not earlier than ``last`` (the previous chunk's last time)."""
+    decrease, and the first is not earlier than ``last`` (the previous chunk's last time).  With ``sources``
+    (check_sources' array) all of this holds within each source, not over the merged lines, and ``last`` is
+    a dict source -> that source's last time."""
     if times is None:
         raise ValueError("a repeat window needs the lines' arrival times (times=)")
     t = np.asarray(times)
@@ -77,16 +116,41 @@ def check_times(times, n: int, last: Optional[int] = None) -> np.ndarray:
     t = t.astype(np.int64, copy=False)   # an int64 array is taken as it is: the caller keeps it unchanged
     if len(t) != n:
         raise ValueError(f"times: {len(t)} times for {n} lines")
+    if sources is not None:
+        order = np.argsort(sources, kind="stable")
+        ts, ss = t[order], sources[order]
+        if n and bool(((ts[1:] < ts[:-1]) & (ss[1:] == ss[:-1])).any()):
+            raise ValueError("times must not decrease over a source's lines")
+        if n and last:
+            first = np.concatenate([[True], ss[1:] != ss[:-1]])
+            for sid, t0 in zip(ss[first].tolist(), ts[first].tolist()):
+                if last.get(sid) is not None and t0 < last[sid]:
+                    raise ValueError("times must not decrease over a source's lines")
+        return t
     if n and (bool((t[1:] < t[:-1]).any()) or (last is not None and int(t[0]) < last)):
         raise ValueError("times must not decrease over a stream's lines")
     return t
 
 
-def collapse_objects(out: list, times=None, window_us: Optional[int] = None, carry: Optional[list] = None) -> np.ndarray:
+def collapse_objects(out: list, times=None, window_us: Optional[int] = None, carry: Optional[list] = None,
+                     sources=None) -> np.ndarray:
     """parse_lines' list with every repeat's slot replaced by [] (in place) -> the mask uint8[n].
     ``window_us``: the time window W with the lines' ``times`` (microseconds); None: no expiry.
     ``carry``: [K, T, last time] of the stream so far ([None, 0, None] starts one), updated in place: the
-    call continues that stream instead of starting one."""
+    call continues that stream instead of starting one.  ``sources``: one source id per line; every
+    source's lines are a stream of their own, and ``carry`` is a dict source -> [K, T, last time]."""
+    if sources is not None:
+        src = check_sources(sources, len(out))
+        if window_us is not None:
+            times = check_times(times, len(out), {s: c[2] for s, c in (carry or {}).items()}, src)
+        mask = np.zeros(len(out), np.uint8)
+        for sid, idx in by_source(src):
+            sub = [out[i] for i in idx]
+            c = carry.setdefault(sid, [None, 0, None]) if carry is not None else None
+            mask[idx] = collapse_objects(sub, None if window_us is None else times[idx], window_us, c)
+            for i, x in zip(idx.tolist(), sub):
+                out[i] = x
+        return mask
     if window_us is not None:
         times = check_times(times, len(out), carry[2] if carry else None).tolist()
     mask = np.zeros(len(out), np.uint8)
@@ -254,4 +318,49 @@ class RepeatTracker:
                 mask[i] = 0
                 self.true_t = int(t[i])
             self.true_key = k
+        return mask
+
+
+class SourceTrackers:
+    """One RepeatTracker per source id of a stream that merges several receivers: every source's lines of a
+    chunk are that source's stream, so the repair around host-resolved rows runs over each source's
+    subsequence of the chunk with the source's own carried keys."""
+
+    def __init__(self):
+        self.trackers: Dict[int, RepeatTracker] = {}
+
+    def fix_chunk(self, sources: np.ndarray, rep: np.ndarray, has_key: np.ndarray, dev_key_of: Callable[[int], Key],
+                  host_keys: Dict[int, Optional[Key]], redo: Iterable[int] = (),
+                  fetch_key: Optional[Callable[[int], Optional[Key]]] = None, table=None,
+                  times=None, window_us: Optional[int] = None) -> np.ndarray:
+        """RepeatTracker.fix_chunk per source -> the chunk's exact mask.  ``sources``: int32[n], the lines'
+        ids; ``table``: the compact per-source table the device left behind this chunk
+        (runtime.REPEAT_SOURCE_ENTRY per source): its ``last`` names the source's last result-bearing device
+        line, whose key is the one the source's slot holds; the other arguments as RepeatTracker.fix_chunk,
+        by line index of the chunk."""
+        rep = np.asarray(rep)
+        has_key = np.asarray(has_key, bool)
+        mask = np.array(rep, np.uint8, copy=True)
+        redo = set(redo)
+        t = None if window_us is None else np.asarray(times)
+        hrows = np.fromiter(host_keys, np.int64, len(host_keys))
+        hsrc = set(sources[hrows].tolist()) if len(hrows) else set()
+        for sid, idx in by_source(np.asarray(sources)):
+            tr = self.trackers.get(sid)
+            if tr is None:
+                tr = self.trackers[sid] = RepeatTracker()
+            pos = None
+            if sid in hsrc:   # chunk index -> index inside the source's subsequence, for its host rows
+                pos = {int(g): j for j, g in enumerate(idx.tolist()) if g in host_keys}
+            hk = {j: host_keys[g] for g, j in pos.items()} if pos else {}
+            rd = [j for g, j in pos.items() if g in redo] if pos else []
+            at = idx.tolist()
+            end_key = None
+            if window_us is None and table is not None and not hk:
+                last = int(table[sid]["last"])
+                if 0 <= last < len(rep) and has_key[last]:
+                    end_key = dev_key_of(last)
+            mask[idx] = tr.fix_chunk(rep[idx], has_key[idx], lambda j: dev_key_of(at[j]), hk, rd,
+                                     None if fetch_key is None else (lambda j: fetch_key(at[j])), end_key,
+                                     **({} if window_us is None else {"times": t[idx], "window_us": window_us}))
         return mask

@@ -49,7 +49,22 @@ EXPORTED = ["sdx_abi_version", "sdx_last_error", "sdx_source_hash", "sdx_layout_
             "sdx_fill_async", "sdx_demod_step", "sdx_group_step", "sdx_split_work_bytes", "sdx_split_lines",
             "sdx_host_count_byte", "sdx_serialize_json_skip", "sdx_mark_repeats", "sdx_repeat_state_bytes",
             "sdx_repeat_scratch_bytes", "sdx_repeat_tile", "sdx_mark_repeats_timed", "sdx_repeat_timed_state_bytes",
-            "sdx_repeat_timed_scratch_bytes"]
+            "sdx_repeat_timed_scratch_bytes", "sdx_mark_repeats_by_source", "sdx_repeat_sources_state_bytes",
+            "sdx_repeat_sources_scratch_bytes"]
+REPEAT_SOURCES_MAX = 4096   # SDX_REPEAT_SOURCES_MAX
+# sdx_repeat_source_entry (csrc/sdx_repeat_layout.h): a source's slot header after a chunk + its last result-bearing line
+REPEAT_SOURCE_ENTRY = np.dtype([("valid", "<u4"), ("kind", "<u4"), ("proto", "<u4"), ("len", "<u4"), ("t", "<i8"),
+                                ("last", "<i4"), ("pad", "<i4")])
+REPEAT_SLOT_HDR = 24        # sizeof(sdx_repeat_timed_state_hdr): a slot's payload bytes follow it
+
+
+def _n_sources(sources) -> int:
+    s = int(sources)
+    if not 1 <= s <= REPEAT_SOURCES_MAX:
+        raise ValueError(f"repeat sources: 1 to {REPEAT_SOURCES_MAX}, not {sources}")
+    return s
+
+
 GROUP_MIN = int(os.environ.get("SDX_GROUP_MIN", "4096"))   # SDX_GROUP_MIN (the env: A/B of the grouping)
 
 
@@ -253,6 +268,13 @@ def load_library(path: Optional[str] = None):
     lib.sdx_repeat_timed_state_bytes.restype = c_size_t
     lib.sdx_repeat_timed_scratch_bytes.argtypes = [c_int32]
     lib.sdx_repeat_timed_scratch_bytes.restype = c_size_t
+    lib.sdx_mark_repeats_by_source.argtypes = [c_void_p, POINTER(SdxJsonIn), c_int, c_int32, c_void_p, c_int32, c_void_p,
+                                               ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.sdx_mark_repeats_by_source.restype = c_int
+    lib.sdx_repeat_sources_state_bytes.argtypes = [c_int32]
+    lib.sdx_repeat_sources_state_bytes.restype = c_size_t
+    lib.sdx_repeat_sources_scratch_bytes.argtypes = [c_int32, c_int32]
+    lib.sdx_repeat_sources_scratch_bytes.restype = c_size_t
     lib.sdx_parse_lines.argtypes = [POINTER(SdxLines), POINTER(SdxLinesOut), c_void_p]
     lib.sdx_parse_lines.restype = c_int
     lib.sdx_select_lines.argtypes = [POINTER(SdxLinesOut), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
@@ -707,11 +729,15 @@ class Engine:
     def repeat_tile(self) -> int:
         return int(self.lib.sdx_repeat_tile())
 
-    def alloc_repeat_state(self, timed: bool = False):
+    def alloc_repeat_state(self, timed: bool = False, sources: Optional[int] = None):
         """The carried state of one stream of lines, zeroed: no previous result-bearing line.
-        ``timed``: the state of mark_repeats_timed (a layout of its own: header, T, payload)."""
+        ``timed``: the state of mark_repeats_timed (a layout of its own: header, T, payload);
+        ``sources``: the state of mark_repeats_by_source, one slot of the timed layout per source id."""
         t = self.torch
-        size = self.lib.sdx_repeat_timed_state_bytes() if timed else self.lib.sdx_repeat_state_bytes()
+        if sources is not None:
+            size = self.lib.sdx_repeat_sources_state_bytes(_n_sources(sources))
+        else:
+            size = self.lib.sdx_repeat_timed_state_bytes() if timed else self.lib.sdx_repeat_state_bytes()
         return t.zeros(int(size), dtype=t.uint8, device=self.dev)
 
     def alloc_repeat(self, n: int):
@@ -760,6 +786,40 @@ class Engine:
         st = self.stream_ptr() if stream is None else c_void_p(stream.cuda_stream)
         _check(self.lib, self.lib.sdx_mark_repeats_timed(self.handle, arr, len(json_ins), n, _ptr(times), int(window_us),
                                                          _ptr(repeat), _ptr(scratch), _ptr(state), st))
+
+    def alloc_repeat_sources(self, n: int, sources: int):
+        """(repeat mask uint8[n], scratch) of mark_repeats_by_source for chunks of up to n lines of ``sources`` ids."""
+        t = self.torch
+        size = self.lib.sdx_repeat_sources_scratch_bytes(max(n, 1), _n_sources(sources))
+        return (t.zeros(max(n, 1), dtype=t.uint8, device=self.dev), t.empty(int(size), dtype=t.uint8, device=self.dev))
+
+    def mark_repeats_by_source(self, json_ins, n: int, source, sources: int, times, window_us, repeat, scratch, state,
+                               stream=None) -> None:
+        """sdx_mark_repeats_by_source on ``stream`` (default: the current one; no host sync): every source id's
+        lines are decided as a stream of their own.  ``source``: a device int32 tensor, one id in
+        [0, sources) per line; ``times`` / ``window_us``: as mark_repeats_timed, non-decreasing within each
+        source, or None / None for no window (both preconditions are the caller's: frontend / stream check
+        them); ``scratch``: alloc_repeat_sources(n, sources)'s; ``state``: alloc_repeat_state(sources=)."""
+        n = int(n)
+        if not 1 <= len(json_ins) <= 4:
+            raise ValueError("mark_repeats_by_source: 1 to 4 kinds")
+        size = lambda x: x.numel() * x.element_size()   # noqa: E731
+        if 1 <= sources <= REPEAT_SOURCES_MAX and (
+                size(repeat) < n or (source is not None and size(source) < 4 * n) or
+                (times is not None and size(times) < 8 * n) or
+                size(scratch) < int(self.lib.sdx_repeat_sources_scratch_bytes(n, sources)) or
+                size(state) < int(self.lib.sdx_repeat_sources_state_bytes(sources))):
+            raise ValueError("mark_repeats_by_source: a buffer is too small for n and sources")
+        arr = (SdxJsonIn * len(json_ins))(*json_ins)
+        st = self.stream_ptr() if stream is None else c_void_p(stream.cuda_stream)
+        _check(self.lib, self.lib.sdx_mark_repeats_by_source(
+            self.handle, arr, len(json_ins), n, _ptr(source), int(sources), _ptr(times),
+            0 if window_us is None else int(window_us), _ptr(repeat), _ptr(scratch), _ptr(state), st))
+
+    def repeat_sources_table(self, scratch, sources: int):
+        """The compact per-source table mark_repeats_by_source left in ``scratch``: a device uint8 view
+        (copy it to the host and read it with REPEAT_SOURCE_ENTRY)."""
+        return scratch[16: 16 + REPEAT_SOURCE_ENTRY.itemsize * int(sources)]
 
     def alloc_json(self, items: int, cap: int):
         t, d = self.torch, self.dev

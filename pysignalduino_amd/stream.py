@@ -163,6 +163,7 @@ class ChunkResult:
         self.wire = self.layout = None
         self.host = {}            # line -> result of the batch API (fallback lines)
         self.repeat = None        # collapse_repeats: uint8[n], 1 = the line repeats the previous result-bearing one
+        self.source = None        # repeat_sources: int32[n], the lines' source ids as submitted (a copy)
         self.affix = {}
         # the chunk's text, for line(i): the submitted sequence, or packed (data, offsets), or a
         # submit_bytes chunk's bytes (_ChunkBytes) + the device's offsets
@@ -279,7 +280,15 @@ class _Slot:
             self.h_sizes = t.zeros(runtime.XCHG_COUNTS * len(self.outs) + 4 * len(self.outs), dtype=t.int32).pin_memory()
             cap = sum(16 * C + 8 * o["rec_cap"] + o["heap_cap"] + 64 for o in self.outs.values())
             self.h_out = t.empty(cap + 3 * C + 64, dtype=t.uint8).pin_memory()
-        if ls.collapse and ls.window_us is not None:   # the timed pass: its scratch, the chunk's arrival times
+        if ls.collapse and ls.n_sources is not None:   # the by-source pass: the chunk's ids, the compact table read back
+            self.rep, self.rep_scratch = eng.alloc_repeat_sources(C, ls.n_sources)
+            self.d_src = t.zeros(C, dtype=t.int32, device=eng.dev)
+            self.h_src = t.zeros(C, dtype=t.int32).pin_memory()
+            self.h_table = t.zeros(runtime.REPEAT_SOURCE_ENTRY.itemsize * ls.n_sources, dtype=t.uint8).pin_memory()
+            if ls.window_us is not None:
+                self.d_times = t.zeros(C, dtype=t.int64, device=eng.dev)
+                self.h_times = t.zeros(C, dtype=t.int64).pin_memory()
+        elif ls.collapse and ls.window_us is not None:   # the timed pass: its scratch, the chunk's arrival times
             self.rep, self.rep_scratch = eng.alloc_repeat_timed(C)
             self.d_times = t.zeros(C, dtype=t.int64, device=eng.dev)
             self.h_times = t.zeros(C, dtype=t.int64).pin_memory()
@@ -296,6 +305,7 @@ class _Slot:
         self.ev = None
         self.src = None           # a submit_bytes chunk: its _ChunkBytes (the offsets come back in stage C)
         self.times = None         # repeat_window: the chunk's arrival times, int64[n] (a host copy for _fix_repeats)
+        self.sources = None       # repeat_sources: the chunk's source ids, int32[n] (the same)
 
 
 class LineStream:
@@ -305,7 +315,12 @@ class LineStream:
     GPU (slots = lag + 1); ``collapse_repeats`` / ``repeat_window`` (seconds): repeat suppression, with a
     window every submit carries arrival times in integer microseconds, non-decreasing over the stream
     (repeats.py): ``submit(lines, times=)`` and ``submit_packed(..., times=)`` one per line,
-    ``submit_bytes(buf, time=)`` one per read buffer.
+    ``submit_bytes(buf, time=)`` one per read buffer.  ``repeat_sources`` = S (with collapse_repeats): the
+    stream merges S receivers and repeat suppression runs per source id: ``submit(lines,
+    sources=)`` and ``submit_packed(..., sources=)`` take one id in [0, S) per line, ``submit_bytes(buf,
+    source=)`` one per read buffer -- the stream keeps one carried tail and one last time per source, so
+    read buffers of different receivers may be handed over alternately; times need not decrease within a
+    source only.  ChunkResult.source holds the ids beside ``repeat``.
 
     submit(lines) -> chunk id; ``submit_packed(data, offsets)`` the same for lines already packed as
     (uint8 bytes, int64 offsets[n + 1]); ``submit_bytes(buf)`` -> chunk ids for a transport's raw read
@@ -314,7 +329,8 @@ class LineStream:
     order (never blocks on a chunk newer than ``lag`` submits); drain() -> all of them (blocks)."""
 
     def __init__(self, parser, chunk_lines: int = 250_000, chunk_bytes: Optional[int] = None, output: str = "json",
-                 lag: int = 3, collapse_repeats: bool = False, repeat_window: Optional[float] = None):
+                 lag: int = 3, collapse_repeats: bool = False, repeat_window: Optional[float] = None,
+                 repeat_sources: Optional[int] = None):
         if output not in ("json", "wire"):
             raise ValueError("output must be 'json' or 'wire'")
         self.collapse = bool(collapse_repeats)
@@ -323,6 +339,11 @@ class LineStream:
         if self.window_us is not None and not self.collapse:
             raise ValueError("repeat_window needs collapse_repeats=True")
         self._last_time = None    # repeat_window: the last submitted line's time
+        self.n_sources = None if repeat_sources is None else runtime._n_sources(repeat_sources)
+        if self.n_sources is not None and not self.collapse:
+            raise ValueError("repeat_sources needs collapse_repeats=True")
+        self._last_times = {}     # repeat_sources with a window: source -> its last submitted line's time
+        self._carries = {}        # repeat_sources, submit_bytes: source -> its unterminated tail
         import torch
         self.torch = torch
         self.parser = parser
@@ -336,11 +357,12 @@ class LineStream:
         if self.collapse:
             # repeat suppression: ONE state per stream, written by every chunk's state pass;
             # rep_ev orders the next chunk's sdx_mark_repeats (on the other demodulation stream) behind it
-            from .repeats import RepeatTracker
-            self.rep_state = (self.eng.alloc_repeat_state() if self.window_us is None else
+            from .repeats import RepeatTracker, SourceTrackers
+            self.rep_state = (self.eng.alloc_repeat_state(sources=self.n_sources) if self.n_sources is not None else
+                              self.eng.alloc_repeat_state() if self.window_us is None else
                               self.eng.alloc_repeat_state(timed=True))
             self.rep_ev = None
-            self.tracker = RepeatTracker()
+            self.tracker = SourceTrackers() if self.n_sources is not None else RepeatTracker()
         self.slots = [_Slot(self) for _ in range(self.lag + 1)]
         dev = self.eng.dev
         # the parse at the highest priority: the host waits for chunk k's class counts before it can
@@ -363,34 +385,49 @@ class LineStream:
         self._carry = bytearray()  # submit_bytes: the unterminated tail of the calls so far
 
     # -- public ------------------------------------------------------------------------------------------
-    def submit(self, lines: Sequence[Union[str, bytes]], times=None) -> int:
+    def submit(self, lines: Sequence[Union[str, bytes]], times=None, sources=None) -> int:
         from .frontend import pack_lines
-        times = self._check_times(times, len(lines))   # before anything is packed or launched
+        sources = self._check_sources(sources, len(lines))   # before anything is packed or launched
+        times = self._check_times(times, len(lines), sources)
         data, offsets, bad = pack_lines(lines, copy=False)   # read once, into the slot's pinned buffer
-        return self.submit_packed(data, offsets, lines=lines, bad=bad, times=times)
+        return self.submit_packed(data, offsets, lines=lines, bad=bad, times=times, sources=sources)
 
-    def _check_times(self, times, n: int):
+    def _check_sources(self, sources, n: int):
+        """A chunk's source ids as int32[n] (None on a stream without repeat_sources); ValueError when they
+        are missing, given to a stream without repeat_sources, or outside [0, S)."""
+        if self.n_sources is None:
+            if sources is not None:
+                raise ValueError("sources given, but the stream has no repeat_sources")
+            return None
+        from .repeats import check_sources
+        return check_sources(sources, n, self.n_sources)
+
+    def _check_times(self, times, n: int, sources=None):
         """A chunk's arrival times as int64[n] (None without a window); ValueError when they are missing,
-        decrease, or start before the previous chunk's last one."""
+        decrease, or start before the previous chunk's last one -- with ``sources`` within each source."""
         if self.window_us is None:
             if times is not None:
                 raise ValueError("times given, but the stream has no repeat_window")
             return None
         from .repeats import check_times
+        if sources is not None:
+            return check_times(times, n, self._last_times, sources)
         return check_times(times, n, self._last_time)
 
-    def submit_packed(self, data, offsets: np.ndarray, lines=None, bad=None, times=None) -> int:
+    def submit_packed(self, data, offsets: np.ndarray, lines=None, bad=None, times=None, sources=None) -> int:
         """``data``: the lines' bytes as a numpy uint8 array (copied into the slot's pinned buffer) or
         a PINNED torch uint8 tensor (uploaded from where it is, no host copy: keep it unchanged until
         the chunk has been collected); ``offsets``: int64[n + 1] into it; ``times``: with a
-        ``repeat_window``, the n arrival times (integer microseconds)."""
+        ``repeat_window``, the n arrival times (integer microseconds); ``sources``: with
+        ``repeat_sources``, the n source ids."""
         n = len(offsets) - 1
         if n > self.C or int(offsets[-1] - offsets[0]) > self.B:
             raise ValueError(f"chunk of {n} lines / {int(offsets[-1] - offsets[0])} bytes exceeds the stream's "
                              f"capacity ({self.C} lines, {self.B} bytes)")
-        times = self._check_times(times, n)
+        sources = self._check_sources(sources, n)
+        times = self._check_times(times, n, sources)
         s = self._take_slot(n)
-        self._set_times(s, times)
+        self._set_times(s, times, sources)
         s.lines, s.bad = lines, bad or {}
         s.data, s.offsets = data, offsets
         self._stage_a(s, data, offsets)
@@ -407,21 +444,33 @@ class LineStream:
         self.next_id += 1
         return s
 
-    def _set_times(self, s: _Slot, times) -> None:
-        """The chunk's checked times into its slot's pinned buffer (stage A uploads them with the chunk)."""
-        s.times = None
+    def _set_times(self, s: _Slot, times, sources=None) -> None:
+        """The chunk's checked times (and source ids) into its slot's pinned buffers (stage A uploads them
+        with the chunk)."""
+        s.times = s.sources = None
+        if sources is not None:
+            n = len(sources)
+            s.sources = s.h_src.numpy()[:n]
+            s.sources[:] = sources
         if times is not None:
             n = len(times)
             s.times = s.h_times.numpy()[:n]     # the slot's own copy: the caller's array may change
             s.times[:] = times
-            if n:
+            if n and sources is not None:       # every source's last line of the chunk
+                ids, back = np.unique(s.sources[::-1], return_index=True)
+                for sid, j in zip(ids.tolist(), (n - 1 - back).tolist()):
+                    self._last_times[sid] = int(s.times[j])
+            elif n:
                 self._last_time = int(times[-1])
 
     def _upload_times(self, s: _Slot) -> None:
-        """On the input stream, in front of the chunk's h2d event: 8 bytes per line."""
+        """On the input stream, in front of the chunk's h2d event: 8 bytes per line, 4 for its source id."""
         if s.times is not None and s.n:
             runtime.copy_async(s.d_times[: s.n], s.h_times[: s.n], self.cin)
             self.h2d_bytes += 8 * s.n
+        if s.sources is not None and s.n:
+            runtime.copy_async(s.d_src[: s.n], s.h_src[: s.n], self.cin)
+            self.h2d_bytes += 4 * s.n
 
     def _queued(self, s: _Slot) -> int:
         self.inflight.append(s)
@@ -431,7 +480,7 @@ class LineStream:
                 self._advance(self.inflight[-1 - age], want)
         return s.cid
 
-    def submit_bytes(self, buf, final: bool = False, time: Optional[int] = None) -> List[int]:
+    def submit_bytes(self, buf, final: bool = False, time: Optional[int] = None, source: Optional[int] = None) -> List[int]:
         """A transport's read buffer, raw: ``buf`` is bytes-like (copied into the slot's pinned buffer) or
         a PINNED torch uint8 tensor (uploaded from where it is: keep it unchanged until its chunks have
         been collected), of any size.  Every '\\n' ends a line (StreamReader.readline(),
@@ -443,8 +492,20 @@ class LineStream:
         line and what follows it in ``buf`` are not taken.  ``time``: with a ``repeat_window``, the arrival
         time of this read buffer (integer microseconds, not earlier than the previous one's).  A line gets
         the time of the buffer that holds its terminating newline -- when StreamReader.readline() would
-        have returned it --, an unterminated tail made the last line the time of the last buffer."""
+        have returned it --, an unterminated tail made the last line the time of the last buffer.
+        ``source``: with ``repeat_sources``, the receiver this buffer was read from: every line of the chunks
+        it queues has that id, the tail is carried to the next buffer of the SAME source, and ``time`` must
+        not be earlier than that source's previous one."""
         t = self.torch
+        if self.n_sources is None:
+            if source is not None:
+                raise ValueError("source given, but the stream has no repeat_sources")
+        else:
+            if source is None or int(source) != source or not 0 <= int(source) < self.n_sources:
+                raise ValueError(f"a stream with repeat_sources needs the read buffer's source id (source=) "
+                                 f"inside [0, {self.n_sources})")
+            source = int(source)
+        last_time = self._last_time if source is None else self._last_times.get(source)
         if self.window_us is None:
             if time is not None:
                 raise ValueError("time given, but the stream has no repeat_window")
@@ -454,9 +515,12 @@ class LineStream:
             if time is not None:
                 if int(time) != time:
                     raise ValueError("time: integer microseconds")
-                if self._last_time is not None and int(time) < self._last_time:
+                if last_time is not None and int(time) < last_time:
                     raise ValueError("times must not decrease over a stream's lines")
-                self._last_time = int(time)
+                if source is None:
+                    self._last_time = int(time)
+                else:
+                    self._last_times[source] = int(time)
         if isinstance(buf, (bytes, bytearray)):
             arr = np.frombuffer(buf, np.uint8)
             view = buf if len(buf) <= 2 * _NlView.PART else _NlView(arr)   # a read buffer: bytes' own rfind / count
@@ -466,26 +530,42 @@ class LineStream:
         pinned = isinstance(buf, t.Tensor) and buf.is_pinned()
         N, lo, ids = len(arr), 0, []
         while True:
-            hi, n = cut_bytes(view, lo, len(self._carry), self.C, self.B)
+            hi, n = cut_bytes(view, lo, len(self._tail(source)), self.C, self.B)
             if hi == lo:
                 break
-            ids.append(self._submit_piece(buf if pinned else None, arr, lo, hi, n, False))
+            ids.append(self._submit_piece(buf if pinned else None, arr, lo, hi, n, False, source))
             lo = hi
-        self._carry += arr[lo:N].tobytes()     # short: less than one line
-        if final and self._carry:
-            ids.append(self._submit_piece(None, arr, N, N, 1, True))
+        self._tail(source).extend(arr[lo:N].tobytes())     # short: less than one line
+        if final and self._tail(source):
+            ids.append(self._submit_piece(None, arr, N, N, 1, True, source))
         return ids
 
-    def close_bytes(self) -> List[int]:
-        """End of the byte stream: a carried tail becomes the last line (submit_bytes(b"", final=True))."""
-        return self.submit_bytes(b"", final=True)
+    def _tail(self, source: Optional[int]) -> bytearray:
+        """The carried, unterminated tail: the stream's, with repeat_sources that of one source."""
+        return self._carry if source is None else self._carries.setdefault(source, bytearray())
 
-    def _submit_piece(self, pinned_buf, arr: np.ndarray, lo: int, hi: int, n: int, final: bool) -> int:
-        carry, self._carry = self._carry, bytearray()
+    def close_bytes(self, source: Optional[int] = None) -> List[int]:
+        """End of the byte stream: a carried tail becomes the last line (submit_bytes(b"", final=True)).
+        With ``repeat_sources``: every source's tail, in id order, or only that of ``source``."""
+        if self.n_sources is None:
+            return self.submit_bytes(b"", final=True, **({} if source is None else {"source": source}))
+        ids = []
+        for sid in (sorted(self._carries) if source is None else [source]):
+            ids += self.submit_bytes(b"", final=True, source=sid)
+        return ids
+
+    def _submit_piece(self, pinned_buf, arr: np.ndarray, lo: int, hi: int, n: int, final: bool,
+                      source: Optional[int] = None) -> int:
+        if source is None:
+            carry, self._carry = self._carry, bytearray()
+        else:
+            carry, self._carries[source] = self._tail(source), bytearray()
         s = self._take_slot(n)
         s.lines, s.bad = None, {}
         s.data = s.offsets = None
-        self._set_times(s, None if self.window_us is None else np.full(n, self._last_time, np.int64))
+        when = self._last_time if source is None else self._last_times.get(source)
+        self._set_times(s, None if self.window_us is None else np.full(n, when, np.int64),
+                        None if source is None else np.full(n, source, np.int32))
         self._stage_a_bytes(s, np.frombuffer(bytes(carry), np.uint8), pinned_buf, arr, lo, hi, final)
         return self._queued(s)
 
@@ -681,7 +761,13 @@ class LineStream:
                 if self.rep_ev is not None:
                     sd.wait_event(self.rep_ev)
                 ins = [eng.json_in(kd, s.outs[name], lo, n, 2) for name, kd, _, _ in _KINDS if name in s.outs]
-                if self.window_us is None:
+                if self.n_sources is not None:   # the ids (and times) came up with the chunk's bytes; the compact
+                    # table back in one copy: every source's header and last result-bearing line
+                    eng.mark_repeats_by_source(ins, n, s.d_src, self.n_sources,
+                                               None if self.window_us is None else s.d_times, self.window_us, s.rep,
+                                               s.rep_scratch, self.rep_state, stream=sd)
+                    runtime.copy_async(s.h_table, eng.repeat_sources_table(s.rep_scratch, self.n_sources), sd)
+                elif self.window_us is None:
                     eng.mark_repeats(ins, n, s.rep, s.rep_scratch, self.rep_state, stream=sd)
                     runtime.copy_async(s.h_state, self.rep_state[:_STATE_HEAD], sd)
                 else:   # the chunk's times came up with its bytes (stage A, in front of the parse)
@@ -752,7 +838,8 @@ class LineStream:
             s.kb = b
             if self.collapse:
                 runtime.copy_async(ho[b + 2 * n: b + 3 * n], s.rep[:n], self.cout)
-                self.d2h_bytes += n + (_STATE_HEAD if self.window_us is None else 0)
+                self.d2h_bytes += n + (s.h_table.numel() if self.n_sources is not None else
+                                       _STATE_HEAD if self.window_us is None else 0)
             if s.src is not None:   # a submit_bytes chunk: the offsets the device found, for line(i)
                 runtime.copy_async(s.h_offs[: n + 1], lb.offsets[: n + 1], self.cout)
                 self.d2h_bytes += 8 * (n + 1)
@@ -837,6 +924,14 @@ class LineStream:
                 return text_key(name_of(i), bytes(blob[o: o + int(r.len[i])]).decode("ascii"))
         else:
             has_key, dev_key_of = self._wire_keys(r)
+        if self.n_sources is not None:   # one tracker per source, over the source's lines of the chunk
+            r.source = s.sources.copy()
+            mask = self.tracker.fix_chunk(r.source, rep, has_key, dev_key_of, host_keys, redo, fetch,
+                                          table=s.h_table.numpy().view(runtime.REPEAT_SOURCE_ENTRY),
+                                          **({} if self.window_us is None else
+                                             {"times": s.times, "window_us": self.window_us}))
+            self._apply_mask(s, r, rep, mask, host_keys, fetched)
+            return
         if self.window_us is not None:   # the tracker follows (K, T) from the mask, the keys and the times
             mask = self.tracker.fix_chunk(rep, has_key, dev_key_of, host_keys, redo, fetch, times=s.times,
                                           window_us=self.window_us)
