@@ -5,18 +5,17 @@
 // REPEAT when (kind, proto index, payload bytes) of its first result equal those of the previous
 // result-bearing line of the stream; lines without results neither start nor break a run.
 //
-// Four launches on the caller's stream, no look-back and no spinning (as sdx_split.hip):
-//   k_rep_keys     lane = line: the kinds' descriptors -> one 16-byte key per line, and per tile of
-//                  SDX_REPEAT_TILE lines its last result-bearing line
-//   k_rep_tiles    one workgroup: running maximum over the tile table -> the last result-bearing line
-//                  in front of every tile, and the chunk's last one
-//   k_rep_resolve  lane = line: the predecessor from the wave's ballot, the tile's waves (LDS), the tile
-//                  table or the carried state; kind / proto / length, then the payload bytes
-//   k_rep_state    one workgroup: key + payload of the chunk's last result-bearing line -> state
+// The file in the order it is written:
+//   helpers   what the kernels share: a key as one 16-byte load, "the last set line of the wave / of the
+//             tile" from a ballot, the predecessor lookup over (ballot, the tile's waves, the tile table),
+//             key equality, K + payload into a state, an orbit followed over the tiles' exits
+//   kernels   k_rep_* (sdx_mark_repeats), k_rept_* (the timed passes; BS: over positions sorted by source),
+//             k_reps_* (ids, radix sort, gather, the sources' slots), each group under its own comment
+//   host      parse_kinds (the kinds' validation), TimedBufs + launch_timed<BS> (the seven timed launches)
+//   entries   three compositions of those launches on the caller's stream, no look-back and no spinning (as
+//             sdx_split.hip): sdx_mark_repeats; sdx_mark_repeats_timed = k_rep_keys + launch_timed<false>;
+//             sdx_mark_repeats_by_source = keys, ids, sort, gather + launch_timed<true> + k_reps_state
 // Payload bytes are read one at a time, [off, off + len) only: nothing past a payload's end.
-// sdx_mark_repeats_timed (a run also ends when its last published line is too old) follows below, with
-// kernels of its own behind k_rep_keys and k_rep_tiles; sdx_mark_repeats_by_source (one run per source id of
-// a stream that merges several receivers) sorts the lines by id and runs the timed kernels over the result.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -45,8 +44,92 @@ struct Kinds {
   KindIn k[4];  // by enum sdx_kind
 };
 
+// ---- helpers shared by the kernels (T threads = WAVES waves per tile, lane = line or position) --------
 __device__ __forceinline__ int last_bit(uint64_t m) { return 63 - __builtin_clzll(m); }  // m != 0
 
+// a key as one 16-byte load: x = kind, y = proto, z = len, w = off
+__device__ __forceinline__ uint4 load_key(const sdx_repeat_key* key) { return *reinterpret_cast<const uint4*>(key); }
+// line g's key, SDX_REPEAT_NONE behind the chunk
+__device__ __forceinline__ sdx_repeat_key key_at(const sdx_repeat_key* keys, int g, int n) {
+  if (g >= n) return sdx_repeat_key{SDX_REPEAT_NONE, 0, 0, 0};
+  const uint4 v = load_key(keys + g);
+  return sdx_repeat_key{v.x, v.y, v.z, v.w};
+}
+
+// The wave's ballot of ``set``; its last set line (-1 = none) goes to wlast[wave].  Every thread of the
+// tile calls it; the table is read behind a __syncthreads() (pred_of, tile_last_out).
+__device__ __forceinline__ uint64_t wave_last(bool set, int g, int32_t* wlast) {
+  const uint64_t m = __ballot(set);
+  const int lane = threadIdx.x & 63;
+  if (lane == 0) wlast[threadIdx.x >> 6] = m ? (int)(g - lane + last_bit(m)) : -1;
+  return m;
+}
+// thread 0: the tile's last set line = the maximum over the waves' -> out[tile]
+__device__ __forceinline__ void tile_last_out(const int32_t* wlast, int32_t* __restrict__ out) {
+  if (threadIdx.x == 0) {
+    int last = -1;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) last = max(last, wlast[w]);
+    out[blockIdx.x] = last;
+  }
+}
+// The last set line in front of line g (INCL: at or in front of it), -1 = none: from the wave's ballot m,
+// else the tile's earlier waves (wlast), else the table of what stands in front of every tile.
+template <bool INCL>
+__device__ __forceinline__ int pred_of(uint64_t m, int g, const int32_t* wlast, const int32_t* __restrict__ before) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t lower = INCL ? m & (~0ull >> (63 - lane)) : lane ? m & (~0ull >> (64 - lane)) : 0ull;
+  if (lower) return g - lane + last_bit(lower);
+  int p = -1;
+  for (int w = wave - 1; w >= 0 && p < 0; --w) p = wlast[w];
+  if (p < 0) p = before[blockIdx.x];
+  return p;
+}
+
+__device__ __forceinline__ bool same_bytes(const uint8_t* a, const uint8_t* b, uint32_t len) {
+  for (uint32_t i = 0; i < len; ++i)
+    if (a[i] != b[i]) return false;
+  return true;
+}
+// key (its payload at ``mine``) against another line's or a state's (kind, proto, len, payload)
+__device__ __forceinline__ bool same_key(const sdx_repeat_key& key, const uint8_t* mine, uint32_t kind, uint32_t proto,
+                                         uint32_t len, const uint8_t* theirs) {
+  return kind == key.kind && proto == key.proto && len == key.len && same_bytes(mine, theirs, key.len);
+}
+
+// K of a state: the header's fields (either layout's header begins valid, kind, proto, len) ...
+template <class HDR>
+__device__ __forceinline__ void set_key(HDR& h, const uint4& v) {
+  h.valid = 1;
+  h.kind = v.x;
+  h.proto = v.y;
+  h.len = v.z;
+}
+// ... and the payload behind it, by the caller's threads tid, tid + stride, ...
+__device__ __forceinline__ void copy_payload(const Kinds& in, const uint4& v, uint8_t* dst, uint32_t tid, uint32_t stride) {
+  const uint8_t* src = in.k[v.x].heap + v.w;
+  for (uint32_t i = tid; i < v.z; i += stride) dst[i] = src[i];
+}
+
+// An orbit that leaves its tile is followed from tile to tile over the exits, at most nt of them -> its
+// line in the last tile it reaches.  ARR: every line it lands on is entered into its tile's tile_arr.
+template <bool ARR>
+__device__ __forceinline__ int follow_exits(int x, int n, int nt, const int32_t* __restrict__ exitv, int32_t* tile_arr) {
+  for (int it = 0; it < nt; ++it) {
+    const int e = exitv[x];
+    if (e < 0 || e >= n) break;
+    if constexpr (ARR) tile_arr[e / T] = e;
+    x = e;
+  }
+  return x;
+}
+
+// ---- sdx_mark_repeats' kernels ----------------------------------------------------------------------
+//   k_rep_keys     lane = line: the kinds' descriptors -> one 16-byte key per line, and per tile of
+//                  SDX_REPEAT_TILE lines its last result-bearing line
+//   k_rep_tiles    one workgroup: the last result-bearing line in front of every tile, and the chunk's last
+//   k_rep_resolve  lane = line: the predecessor (pred_of) or the carried state; same_key
+//   k_rep_state    one workgroup: key + payload of the chunk's last result-bearing line -> state
 __global__ __launch_bounds__(T) void k_rep_keys(Kinds in, int n, sdx_repeat_key* __restrict__ keys,
                                                 int32_t* __restrict__ tile_last) {
   __shared__ int32_t wlast[WAVES];
@@ -64,15 +147,9 @@ __global__ __launch_bounds__(T) void k_rep_keys(Kinds in, int n, sdx_repeat_key*
     }
     *reinterpret_cast<uint4*>(keys + g) = make_uint4(key.kind, key.proto, key.len, key.off);
   }
-  const uint64_t m = __ballot(key.kind != SDX_REPEAT_NONE);
-  if ((threadIdx.x & 63) == 0) wlast[threadIdx.x >> 6] = m ? (int)(g + last_bit(m)) : -1;
+  wave_last(key.kind != SDX_REPEAT_NONE, g, wlast);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    int last = -1;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) last = max(last, wlast[w]);
-    tile_last[blockIdx.x] = last;
-  }
+  tile_last_out(wlast, tile_last);
 }
 
 // tile_prev[b] = max(tile_last[0 .. b)) (-1 = none), head[0] = max over all tiles: line indices grow
@@ -107,49 +184,29 @@ __global__ __launch_bounds__(ST) void k_rep_tiles(const int32_t* __restrict__ ti
   if (threadIdx.x == 0) head[0] = carry;
 }
 
-__device__ __forceinline__ bool same_bytes(const uint8_t* a, const uint8_t* b, uint32_t len) {
-  for (uint32_t i = 0; i < len; ++i)
-    if (a[i] != b[i]) return false;
-  return true;
-}
-
 __global__ __launch_bounds__(T) void k_rep_resolve(Kinds in, int n, const sdx_repeat_key* __restrict__ keys,
                                                    const int32_t* __restrict__ tile_prev,
                                                    const uint8_t* __restrict__ state, uint8_t* __restrict__ repeat) {
   __shared__ int32_t wlast[WAVES];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = blockIdx.x * T + threadIdx.x;
-  sdx_repeat_key key{SDX_REPEAT_NONE, 0, 0, 0};
-  if (g < n) {
-    const uint4 v = *reinterpret_cast<const uint4*>(keys + g);
-    key = sdx_repeat_key{v.x, v.y, v.z, v.w};
-  }
+  const sdx_repeat_key key = key_at(keys, g, n);
   const bool have = key.kind != SDX_REPEAT_NONE;
-  const uint64_t m = __ballot(have);
-  if (lane == 0) wlast[wave] = m ? (int)(g + last_bit(m)) : -1;
+  const uint64_t m = wave_last(have, g, wlast);
   __syncthreads();
   if (g >= n) return;
   if (!have) {
     repeat[g] = 0;
     return;
   }
-  const uint64_t lower = lane ? m & (~0ull >> (64 - lane)) : 0ull;
-  int pred = -1;
-  if (lower) {
-    pred = g - lane + last_bit(lower);
-  } else {
-    for (int w = wave - 1; w >= 0 && pred < 0; --w) pred = wlast[w];
-    if (pred < 0) pred = tile_prev[blockIdx.x];
-  }
+  const int pred = pred_of<false>(m, g, wlast, tile_prev);
   const uint8_t* mine = in.k[key.kind].heap + key.off;
   bool eq;
   if (pred >= 0) {
-    const uint4 v = *reinterpret_cast<const uint4*>(keys + pred);
-    eq = v.x == key.kind && v.y == key.proto && v.z == key.len && same_bytes(mine, in.k[key.kind].heap + v.w, key.len);
+    const uint4 v = load_key(keys + pred);
+    eq = same_key(key, mine, v.x, v.y, v.z, in.k[key.kind].heap + v.w);
   } else {  // no earlier result-bearing line in this chunk: the carried state
     const sdx_repeat_state_hdr h = *reinterpret_cast<const sdx_repeat_state_hdr*>(state);
-    eq = h.valid && h.kind == key.kind && h.proto == key.proto && h.len == key.len &&
-         same_bytes(mine, state + sizeof(sdx_repeat_state_hdr), key.len);
+    eq = h.valid && same_key(key, mine, h.kind, h.proto, h.len, state + sizeof(sdx_repeat_state_hdr));
   }
   repeat[g] = eq ? 1 : 0;
 }
@@ -158,17 +215,9 @@ __global__ __launch_bounds__(T) void k_rep_state(Kinds in, const sdx_repeat_key*
                                                  const int32_t* __restrict__ head, uint8_t* __restrict__ state) {
   const int last = head[0];
   if (last < 0) return;  // no result-bearing line in this chunk: the state stays
-  const uint4 v = *reinterpret_cast<const uint4*>(keys + last);
-  if (threadIdx.x == 0) {
-    sdx_repeat_state_hdr* h = reinterpret_cast<sdx_repeat_state_hdr*>(state);
-    h->valid = 1;
-    h->kind = v.x;
-    h->proto = v.y;
-    h->len = v.z;
-  }
-  const uint8_t* src = in.k[v.x].heap + v.w;
-  uint8_t* dst = state + sizeof(sdx_repeat_state_hdr);
-  for (uint32_t i = threadIdx.x; i < v.z; i += T) dst[i] = src[i];
+  const uint4 v = load_key(keys + last);
+  if (threadIdx.x == 0) set_key(*reinterpret_cast<sdx_repeat_state_hdr*>(state), v);
+  copy_payload(in, v, state + sizeof(sdx_repeat_state_hdr), threadIdx.x, T);
 }
 
 // ---- sdx_mark_repeats_timed: a run also ends when its anchor is more than W old -----
@@ -182,8 +231,8 @@ __global__ __launch_bounds__(T) void k_rep_state(Kinds in, const sdx_repeat_key*
 //   segment       a head and the lines behind it up to the next head: equal keys, every gap <= W
 //   orbit         inside a segment the published lines are head, succ(head), succ(succ(head)), ... with
 //                 succ(a) = the segment's first line behind a with t > t(a) + W
-// Eight launches, the first two those of sdx_mark_repeats:
-//   k_rep_keys, k_rep_tiles    keys, the last result-bearing line in front of every tile
+// Behind k_rep_keys, seven launches (launch_timed):
+//   k_rep_tiles    the last result-bearing line in front of every tile, as in sdx_mark_repeats
 //   k_rept_heads   lane = line: predecessor as k_rep_resolve, key compare and gap -> flags, te (a line
 //                  without results takes its predecessor's time, so te is non-decreasing and a search
 //                  never stops on such a line), the tile's last head
@@ -193,19 +242,13 @@ __global__ __launch_bounds__(T) void k_rep_state(Kinds in, const sdx_repeat_key*
 //                  (shuffles), behind it galloping over te / seg in memory; then pointer doubling over
 //                  the tile (LDS, 8 rounds): the orbit's last line inside the tile and its first behind it
 //   k_rept_chain   one workgroup, thread = tile: an orbit that leaves its head's tile is followed from
-//                  tile to tile (one load per tile it enters; orbits of different segments in parallel)
-//                  and entered into the tiles it lands in; then the state: K as k_rep_state, T = the
-//                  time of the last line of the last head's orbit
+//                  tile to tile (follow_exits: one load per tile it enters; orbits of different segments in
+//                  parallel) and entered into the tiles it lands in; then the state: K as k_rep_state, T =
+//                  the time of the last line of the last head's orbit
 //   k_rept_mark    lane = line: the tile's heads and its entry walk their orbit inside the tile (LDS)
 // Every search and walk is bounded by indices: on times that decrease the mask is unspecified, but
 // nothing leaves its buffer and every loop ends.
 namespace sdxt {
-using sdxr::Kinds;
-using sdxr::last_bit;
-using sdxr::same_bytes;
-using sdxr::ST;
-using sdxr::T;
-using sdxr::WAVES;
 
 // t - anchor > w for anchor <= t (the precondition), whatever the two values: no signed overflow
 __device__ __forceinline__ bool past(int64_t t, int64_t anchor, int64_t w) {
@@ -239,27 +282,14 @@ __global__ __launch_bounds__(T) void k_rept_heads(Kinds in, int n, const sdx_rep
                                                   int32_t* __restrict__ tile_arr, BySrc bs) {
   __shared__ int32_t wlast[WAVES];
   __shared__ int32_t whead[WAVES];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = blockIdx.x * T + threadIdx.x;
-  sdx_repeat_key key{SDX_REPEAT_NONE, 0, 0, 0};
-  if (g < n) {
-    const uint4 v = *reinterpret_cast<const uint4*>(keys + g);
-    key = sdx_repeat_key{v.x, v.y, v.z, v.w};
-  }
+  const sdx_repeat_key key = key_at(keys, g, n);
   const bool have = key.kind != SDX_REPEAT_NONE;
-  const uint64_t m = __ballot(have);
-  if (lane == 0) wlast[wave] = m ? (int)(g + last_bit(m)) : -1;
+  const uint64_t m = wave_last(have, g, wlast);
   __syncthreads();
   uint32_t f = 0;
   if (g < n) {
-    const uint64_t lower = lane ? m & (~0ull >> (64 - lane)) : 0ull;
-    int pred = -1;
-    if (lower) {
-      pred = g - lane + last_bit(lower);
-    } else {
-      for (int w = wave - 1; w >= 0 && pred < 0; --w) pred = wlast[w];
-      if (pred < 0) pred = tile_prev[blockIdx.x];
-    }
+    const int pred = pred_of<false>(m, g, wlast, tile_prev);
     int64_t t = 0;
     bool inrun = pred >= 0;  // the predecessor decides; otherwise the carried state
     if constexpr (BS) {
@@ -271,16 +301,15 @@ __global__ __launch_bounds__(T) void k_rept_heads(Kinds in, int n, const sdx_rep
       f = SDX_RT_RB;
       const uint8_t* mine = in.k[key.kind].heap + key.off;
       if (inrun) {
-        const uint4 v = *reinterpret_cast<const uint4*>(keys + pred);
-        const bool cont = !past(t, times[pred], window) && v.x == key.kind && v.y == key.proto && v.z == key.len &&
-                          same_bytes(mine, in.k[key.kind].heap + v.w, key.len);
+        const uint4 v = load_key(keys + pred);
+        const bool cont = !past(t, times[pred], window) && same_key(key, mine, v.x, v.y, v.z, in.k[key.kind].heap + v.w);
         if (!cont) f |= SDX_RT_HEAD;
       } else {  // the chunk's first result-bearing line: the carried (K, T)
         const uint8_t* slot = slot_of<BS>(state, bs, g);
         const sdx_repeat_timed_state_hdr h = *reinterpret_cast<const sdx_repeat_timed_state_hdr*>(slot);
         f |= SDX_RT_HEAD;
-        if (h.valid && !past(t, h.t, window) && h.kind == key.kind && h.proto == key.proto && h.len == key.len &&
-            same_bytes(mine, slot + sizeof(sdx_repeat_timed_state_hdr), key.len))
+        if (h.valid && !past(t, h.t, window) &&
+            same_key(key, mine, h.kind, h.proto, h.len, slot + sizeof(sdx_repeat_timed_state_hdr)))
           f |= SDX_RT_SREP;
       }
     } else if (pred >= 0) {
@@ -289,37 +318,20 @@ __global__ __launch_bounds__(T) void k_rept_heads(Kinds in, int n, const sdx_rep
     te[g] = t;
     flags[g] = (uint8_t)f;
   }
-  const uint64_t hm = __ballot((f & SDX_RT_HEAD) != 0);
-  if (lane == 0) whead[wave] = hm ? (int)(g + last_bit(hm)) : -1;
+  wave_last((f & SDX_RT_HEAD) != 0, g, whead);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    int last = -1;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) last = max(last, whead[w]);
-    tile_head[blockIdx.x] = last;
-    tile_arr[blockIdx.x] = -1;
-  }
+  tile_last_out(whead, tile_head);
+  if (threadIdx.x == 0) tile_arr[blockIdx.x] = -1;
 }
 
 __global__ __launch_bounds__(T) void k_rept_seg(int n, const uint8_t* __restrict__ flags,
                                                 const int32_t* __restrict__ tile_prevhead, int32_t* __restrict__ seg) {
   __shared__ int32_t whead[WAVES];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = blockIdx.x * T + threadIdx.x;
-  const bool head = g < n && (flags[g] & SDX_RT_HEAD);
-  const uint64_t hm = __ballot(head);
-  if (lane == 0) whead[wave] = hm ? (int)(g + last_bit(hm)) : -1;
+  const uint64_t hm = wave_last(g < n && (flags[g] & SDX_RT_HEAD), g, whead);
   __syncthreads();
   if (g >= n) return;
-  const uint64_t upto = hm & (~0ull >> (63 - lane));
-  int s = -1;
-  if (upto) {
-    s = g - lane + last_bit(upto);
-  } else {
-    for (int w = wave - 1; w >= 0 && s < 0; --w) s = whead[w];
-    if (s < 0) s = tile_prevhead[blockIdx.x];
-  }
-  seg[g] = s;
+  seg[g] = pred_of<true>(hm, g, whead, tile_prevhead);
 }
 
 template <bool BS>
@@ -410,13 +422,8 @@ __global__ __launch_bounds__(ST) void k_rept_chain(Kinds in, int n, int nt, cons
   for (int b = threadIdx.x; b < nt; b += ST) {
     const int h = tile_head[b];
     if (h < 0) continue;
-    int x = h;  // only a tile's last head can have an orbit that leaves the tile
-    for (int it = 0; it < nt; ++it) {
-      const int e = exitv[x];
-      if (e < 0 || e >= n) break;
-      tile_arr[e / T] = e;
-      x = e;
-    }
+    // only a tile's last head can have an orbit that leaves the tile
+    const int x = follow_exits<true>(h, n, nt, exitv, tile_arr);
     if (!BS && h == last_head) {  // T: the last published line; it stays when the carried anchor covers them all
       const int l = lastv[x];
       if (!(l == h && (flags[h] & SDX_RT_SREP))) sh->t = te[l];
@@ -425,16 +432,9 @@ __global__ __launch_bounds__(ST) void k_rept_chain(Kinds in, int n, int nt, cons
   if constexpr (BS) return;  // the sources' slots: k_reps_state
   const int last = head[0];
   if (last < 0) return;  // no result-bearing line in this chunk: the state stays
-  const uint4 v = *reinterpret_cast<const uint4*>(keys + last);
-  if (threadIdx.x == 0) {
-    sh->valid = 1;
-    sh->kind = v.x;
-    sh->proto = v.y;
-    sh->len = v.z;
-  }
-  const uint8_t* src = in.k[v.x].heap + v.w;
-  uint8_t* dst = state + sizeof(sdx_repeat_timed_state_hdr);
-  for (uint32_t i = threadIdx.x; i < v.z; i += ST) dst[i] = src[i];
+  const uint4 v = load_key(keys + last);
+  if (threadIdx.x == 0) set_key(*sh, v);
+  copy_payload(in, v, state + sizeof(sdx_repeat_timed_state_hdr), threadIdx.x, ST);
 }
 
 template <bool BS>
@@ -485,10 +485,10 @@ __global__ __launch_bounds__(T) void k_rept_mark(int n, const int32_t* __restric
 //                  stable scatter.  No look-back, no global atomics (the scheme of sdx_group.hip's sort).
 //   k_reps_gather  keys, times and ids by position; every source's run [lo, hi); the tiles' last
 //                  result-bearing positions
-//   k_rep_tiles, k_rept_heads<1>, k_rep_tiles, k_rept_seg, k_rept_succ<1>, k_rept_chain<1>
-//   k_rept_mark<1> writes the mask back in line order
+//   launch_timed<true>   over positions; k_rept_mark<1> writes the mask back in line order
 //   k_reps_state   a wave per source: K from the run's last result-bearing line, T from its last head's
-//                  orbit end, the payload copied by the wave; the source's entry of the compact table
+//                  orbit end (follow_exits), the payload copied by the wave; the source's entry of the
+//                  compact table.  Its range checks on what it reads from the scratch are its own.
 namespace sdxs {
 using sdxt::BySrc;
 
@@ -592,7 +592,7 @@ __global__ __launch_bounds__(T) void k_reps_gather(int n, int S, const int32_t* 
     uint4 v = make_uint4(SDX_REPEAT_NONE, 0, 0, 0);
     int64_t t = 0;
     if (line < (uint32_t)n) {
-      if ((uint32_t)source[line] < (uint32_t)S) v = *reinterpret_cast<const uint4*>(lkeys + line);
+      if ((uint32_t)source[line] < (uint32_t)S) v = load_key(lkeys + line);
       if (times) t = times[line];
     }
     *reinterpret_cast<uint4*>(keys + g) = v;
@@ -604,15 +604,9 @@ __global__ __launch_bounds__(T) void k_reps_gather(int n, int S, const int32_t* 
       if (g == n - 1 || psrc[g + 1] != s) run_hi[s] = g + 1;
     }
   }
-  const uint64_t m = __ballot(have);
-  if ((threadIdx.x & 63) == 0) wlast[threadIdx.x >> 6] = m ? (int)(g - (threadIdx.x & 63) + last_bit(m)) : -1;
+  wave_last(have, g, wlast);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    int last = -1;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) last = max(last, wlast[w]);
-    tile_last[blockIdx.x] = last;
-  }
+  tile_last_out(wlast, tile_last);
 }
 
 __global__ __launch_bounds__(T) void k_reps_state(Kinds in, int n, int nt, int S, const sdx_repeat_key* __restrict__ keys,
@@ -634,36 +628,164 @@ __global__ __launch_bounds__(T) void k_reps_state(Kinds in, int n, int nt, int S
   }
   int line = -1;
   if (last >= 0) {  // the source has a result-bearing line in this chunk
-    const uint4 v = *reinterpret_cast<const uint4*>(keys + last);
-    h.valid = 1;
-    h.kind = v.x;
-    h.proto = v.y;
-    h.len = v.z;
+    const uint4 v = load_key(keys + last);
+    set_key(h, v);
     const int hd = seg[hi - 1];  // the run's last head: its first result-bearing line is one
     if (hd >= lo && hd < hi) {
-      int x = hd;  // an orbit that leaves its tile is followed from tile to tile, as k_rept_chain does
-      for (int it = 0; it < nt; ++it) {
-        const int e = exitv[x];
-        if (e < 0 || e >= n) break;
-        x = e;
-      }
-      const int l = lastv[x];
+      const int l = lastv[follow_exits<false>(hd, n, nt, exitv, nullptr)];  // as k_rept_chain follows it
       if (l >= 0 && l < n && !(l == hd && (flags[hd] & SDX_RT_SREP))) h.t = te[l];
     }
     const uint32_t pl = (uint32_t)perm[last];
     line = pl < (uint32_t)n ? (int)pl : -1;
-    if (v.x <= (uint32_t)SDX_KIND_MN && in.k[v.x].heap) {
-      const uint8_t* src = in.k[v.x].heap + v.w;
-      uint8_t* dst = slot + sizeof(sdx_repeat_timed_state_hdr);
-      for (uint32_t i = lane; i < v.z; i += 64) dst[i] = src[i];
-    }
+    if (v.x <= (uint32_t)SDX_KIND_MN && in.k[v.x].heap)
+      copy_payload(in, v, slot + sizeof(sdx_repeat_timed_state_hdr), lane, 64);
     if (lane == 0) *reinterpret_cast<sdx_repeat_timed_state_hdr*>(slot) = h;
   }
   if (lane == 0) table[s] = sdx_repeat_source_entry{h.valid, h.kind, h.proto, h.len, h.t, line, 0};
 }
 
 }  // namespace sdxs
+
+// ---- host: what the three entries share ----------------------------------------------------------------
+static int bad_arg(const char* fn, const char* what) { return sdx::set_error(SDX_EINVAL, std::string(fn) + ": " + what); }
+
+// the checks every entry begins with; parse_kinds relies on them
+static int check_counts(const char* fn, const sdx_json_in* kinds, int k, int32_t n) {
+  if (!kinds || k < 1 || k > 4) return bad_arg(fn, "1 to 4 kinds");
+  if (n < 0) return bad_arg(fn, "n < 0");
+  return SDX_OK;
+}
+// kinds[0 .. k) -> in, every kind at most once, with all three buffers and the chunk's n
+static int parse_kinds(const char* fn, const sdx_json_in* kinds, int k, int32_t n, Kinds& in) {
+  in = Kinds{};
+  for (int i = 0; i < k; ++i) {
+    const sdx_json_in& j = kinds[i];
+    if (j.kind < SDX_KIND_MU || j.kind > SDX_KIND_MN) return bad_arg(fn, "bad kind");
+    if (in.k[j.kind].desc) return bad_arg(fn, "a kind given twice");
+    if (!j.desc_dev || !j.rec_dev || !j.heap_dev) return bad_arg(fn, "null buffer");
+    if (j.n != n) return bad_arg(fn, "every kind's n must be the chunk's n");
+    in.k[j.kind] = KindIn{j.desc_dev, j.rec_dev, j.heap_dev};
+  }
+  return SDX_OK;
+}
+static int launched(const char* fn) {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? SDX_OK : sdx::set_error(SDX_EHIP, std::string(fn) + ": " + hipGetErrorString(e));
+}
+
+// the arrays of the timed passes inside a scratch buffer: by line in sdx_mark_repeats_timed's, by position
+// in sdx_mark_repeats_by_source's (sdx_repeat_layout.h)
+struct TimedBufs {
+  int32_t* head;
+  sdx_repeat_key* keys;
+  int64_t* te;
+  int32_t *seg, *succ, *exitv, *lastv;
+  int32_t *tile_last, *tile_prev, *tile_head, *tile_prevhead, *tile_arr;
+  uint8_t* flags;
+};
+template <class X>
+static X* at(uint8_t* s, size_t off) {
+  return reinterpret_cast<X*>(s + off);
+}
+static TimedBufs timed_bufs(uint8_t* s, int32_t n) {
+  auto tile = [&](int t) { return at<int32_t>(s, sdx_rt_tile_off(n, t)); };
+  return TimedBufs{at<int32_t>(s, 0), at<sdx_repeat_key>(s, sdx_rt_keys_off()), at<int64_t>(s, sdx_rt_te_off(n)),
+                   at<int32_t>(s, sdx_rt_seg_off(n)), at<int32_t>(s, sdx_rt_succ_off(n)), at<int32_t>(s, sdx_rt_exit_off(n)),
+                   at<int32_t>(s, sdx_rt_last_off(n)), tile(0), tile(1), tile(2), tile(3), tile(4), s + sdx_rt_flags_off(n)};
+}
+template <class X>
+static X* part(void* scratch, int32_t n, int S, int p) {  // a part of sdx_mark_repeats_by_source's scratch
+  return at<X>(static_cast<uint8_t*>(scratch), sdx_rs_off(n, S, p));
+}
+static TimedBufs source_bufs(uint8_t* s, int32_t n, int S) {
+  const size_t nt = (size_t)sdx_repeat_tiles(n);
+  int32_t* tiles = part<int32_t>(s, n, S, SDX_RS_TILES);
+  return TimedBufs{part<int32_t>(s, n, S, SDX_RS_HEAD), part<sdx_repeat_key>(s, n, S, SDX_RS_KEYS),
+                   part<int64_t>(s, n, S, SDX_RS_TE), part<int32_t>(s, n, S, SDX_RS_SEG), part<int32_t>(s, n, S, SDX_RS_SUCC),
+                   part<int32_t>(s, n, S, SDX_RS_EXIT), part<int32_t>(s, n, S, SDX_RS_LAST), tiles, tiles + nt,
+                   tiles + 2 * nt, tiles + 3 * nt, tiles + 4 * nt, part<uint8_t>(s, n, S, SDX_RS_FLAGS)};
+}
+
+// The timed passes behind the keys (b.keys, b.tile_last are written): seven launches -> repeat and, BS =
+// false, the state; BS = true leaves the sources' slots to k_reps_state.
+template <bool BS>
+static void launch_timed(const Kinds& in, int n, const TimedBufs& b, const int64_t* times, int64_t window, uint8_t* state,
+                         uint8_t* repeat, const sdxt::BySrc& bs, hipStream_t st) {
+  const int nt = (int)sdx_repeat_tiles(n);
+  const dim3 grid(nt), blk(T), one(1), wide(ST);
+  hipLaunchKernelGGL(k_rep_tiles, one, wide, 0, st, (const int32_t*)b.tile_last, nt, b.tile_prev, b.head);
+  hipLaunchKernelGGL(sdxt::k_rept_heads<BS>, grid, blk, 0, st, in, n, (const sdx_repeat_key*)b.keys,
+                     (const int32_t*)b.tile_prev, times, window, (const uint8_t*)state, b.te, b.flags, b.tile_head,
+                     b.tile_arr, bs);
+  hipLaunchKernelGGL(k_rep_tiles, one, wide, 0, st, (const int32_t*)b.tile_head, nt, b.tile_prevhead, b.head + 1);
+  hipLaunchKernelGGL(sdxt::k_rept_seg, grid, blk, 0, st, n, (const uint8_t*)b.flags, (const int32_t*)b.tile_prevhead, b.seg);
+  hipLaunchKernelGGL(sdxt::k_rept_succ<BS>, grid, blk, 0, st, n, (const int64_t*)b.te, (const int32_t*)b.seg,
+                     (const uint8_t*)b.flags, window, (const uint8_t*)state, b.succ, b.exitv, b.lastv, bs);
+  hipLaunchKernelGGL(sdxt::k_rept_chain<BS>, one, wide, 0, st, in, n, nt, (const sdx_repeat_key*)b.keys,
+                     (const int32_t*)b.head, (const int32_t*)b.tile_head, (const int32_t*)b.exitv, (const int32_t*)b.lastv,
+                     (const int64_t*)b.te, (const uint8_t*)b.flags, b.tile_arr, state);
+  hipLaunchKernelGGL(sdxt::k_rept_mark<BS>, grid, blk, 0, st, n, (const int32_t*)b.succ, (const uint8_t*)b.flags,
+                     (const int32_t*)b.tile_arr, repeat, bs);
+}
 }  // namespace sdxr
+
+// ---- the entries ---------------------------------------------------------------------------------------
+extern "C" size_t sdx_repeat_state_bytes(void) { return sdx_repeat_state_size(); }
+extern "C" size_t sdx_repeat_scratch_bytes(int32_t n) { return sdx_repeat_scratch_size(n); }
+extern "C" int sdx_repeat_tile(void) { return SDX_REPEAT_TILE; }
+
+extern "C" int sdx_mark_repeats(const sdx_bank* bank, const sdx_json_in* kinds, int k, int32_t n, uint8_t* repeat_dev,
+                                void* key_scratch_dev, void* state_dev, void* hip_stream) {
+  using namespace sdxr;
+  static const char FN[] = "sdx_mark_repeats";
+  (void)bank;  // keys are table indices: no bank record is read
+  Kinds in;
+  if (int rc = check_counts(FN, kinds, k, n)) return rc;
+  if (int rc = parse_kinds(FN, kinds, k, n, in)) return rc;
+  // an empty chunk is accepted before the buffers are looked at: the other two entries check theirs first.
+  // Callers may rely on either, so the asymmetry stays.
+  if (n == 0) return SDX_OK;
+  if (!repeat_dev || !key_scratch_dev || !state_dev) return bad_arg(FN, "null buffer");
+  if (((uintptr_t)key_scratch_dev | (uintptr_t)state_dev) & 15)
+    return bad_arg(FN, "key_scratch_dev and state_dev must be 16-byte aligned");
+  uint8_t *s = static_cast<uint8_t*>(key_scratch_dev), *state = static_cast<uint8_t*>(state_dev);
+  int32_t* head = at<int32_t>(s, 0);
+  sdx_repeat_key* keys = at<sdx_repeat_key>(s, sdx_repeat_keys_off());
+  int32_t* tile_last = at<int32_t>(s, sdx_repeat_tile_last_off(n));
+  int32_t* tile_prev = at<int32_t>(s, sdx_repeat_tile_prev_off(n));
+  const int nt = (int)sdx_repeat_tiles(n);
+  hipStream_t st = (hipStream_t)hip_stream;
+  hipLaunchKernelGGL(k_rep_keys, dim3(nt), dim3(T), 0, st, in, (int)n, keys, tile_last);
+  hipLaunchKernelGGL(k_rep_tiles, dim3(1), dim3(ST), 0, st, (const int32_t*)tile_last, nt, tile_prev, head);
+  hipLaunchKernelGGL(k_rep_resolve, dim3(nt), dim3(T), 0, st, in, (int)n, (const sdx_repeat_key*)keys,
+                     (const int32_t*)tile_prev, (const uint8_t*)state, repeat_dev);
+  hipLaunchKernelGGL(k_rep_state, dim3(1), dim3(T), 0, st, in, (const sdx_repeat_key*)keys, (const int32_t*)head, state);
+  return launched(FN);
+}
+
+extern "C" size_t sdx_repeat_timed_state_bytes(void) { return sdx_repeat_timed_state_size(); }
+extern "C" size_t sdx_repeat_timed_scratch_bytes(int32_t n) { return sdx_repeat_timed_scratch_size(n); }
+
+extern "C" int sdx_mark_repeats_timed(const sdx_bank* bank, const sdx_json_in* kinds, int k, int32_t n,
+                                      const int64_t* times_dev, int64_t window_us, uint8_t* repeat_dev,
+                                      void* scratch_dev, void* state_dev, void* hip_stream) {
+  using namespace sdxr;
+  static const char FN[] = "sdx_mark_repeats_timed";
+  (void)bank;
+  Kinds in;
+  if (int rc = check_counts(FN, kinds, k, n)) return rc;
+  if (window_us < 0) return bad_arg(FN, "window_us < 0");
+  if (!times_dev || !repeat_dev || !scratch_dev || !state_dev) return bad_arg(FN, "null buffer");
+  if ((((uintptr_t)scratch_dev | (uintptr_t)state_dev) & 15) || ((uintptr_t)times_dev & 7))
+    return bad_arg(FN, "scratch_dev and state_dev must be 16-byte, times_dev 8-byte aligned");
+  if (int rc = parse_kinds(FN, kinds, k, n, in)) return rc;
+  if (n == 0) return SDX_OK;
+  const TimedBufs b = timed_bufs(static_cast<uint8_t*>(scratch_dev), n);
+  hipStream_t st = (hipStream_t)hip_stream;
+  hipLaunchKernelGGL(k_rep_keys, dim3((int)sdx_repeat_tiles(n)), dim3(T), 0, st, in, (int)n, b.keys, b.tile_last);
+  launch_timed<false>(in, n, b, times_dev, window_us, static_cast<uint8_t*>(state_dev), repeat_dev, sdxt::BySrc{}, st);
+  return launched(FN);
+}
 
 extern "C" size_t sdx_repeat_sources_state_bytes(int32_t n_sources) { return sdx_repeat_sources_state_size(n_sources); }
 extern "C" size_t sdx_repeat_sources_scratch_bytes(int32_t n, int32_t n_sources) {
@@ -674,204 +796,52 @@ extern "C" int sdx_mark_repeats_by_source(const sdx_bank* bank, const sdx_json_i
                                           const int32_t* source_dev, int32_t n_sources, const int64_t* times_dev,
                                           int64_t window_us, uint8_t* repeat_dev, void* scratch_dev, void* state_dev,
                                           void* hip_stream) {
-  namespace sdxt = sdxr::sdxt;
-  namespace sdxs = sdxr::sdxs;
+  using namespace sdxr;
+  static const char FN[] = "sdx_mark_repeats_by_source";
   (void)bank;
-  if (!kinds || k < 1 || k > 4) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: 1 to 4 kinds");
-  if (n < 0) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: n < 0");
-  if (!sdx_rs_sources_ok(n_sources))
-    return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: n_sources must be 1 .. SDX_REPEAT_SOURCES_MAX");
-  if (times_dev && window_us < 0) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: window_us < 0");
-  if (!source_dev || !repeat_dev || !scratch_dev || !state_dev)
-    return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: null buffer");
+  Kinds in;
+  if (int rc = check_counts(FN, kinds, k, n)) return rc;
+  if (!sdx_rs_sources_ok(n_sources)) return bad_arg(FN, "n_sources must be 1 .. SDX_REPEAT_SOURCES_MAX");
+  if (times_dev && window_us < 0) return bad_arg(FN, "window_us < 0");
+  if (!source_dev || !repeat_dev || !scratch_dev || !state_dev) return bad_arg(FN, "null buffer");
   if ((((uintptr_t)scratch_dev | (uintptr_t)state_dev) & 15) || ((uintptr_t)times_dev & 7) || ((uintptr_t)source_dev & 3))
-    return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: scratch_dev and state_dev must be 16-byte, "
-                                      "times_dev 8-byte, source_dev 4-byte aligned");
-  sdxr::Kinds in{};
-  for (int i = 0; i < k; ++i) {
-    const sdx_json_in& j = kinds[i];
-    if (j.kind < SDX_KIND_MU || j.kind > SDX_KIND_MN)
-      return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: bad kind");
-    if (in.k[j.kind].desc) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: a kind given twice");
-    if (!j.desc_dev || !j.rec_dev || !j.heap_dev)
-      return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: null buffer");
-    if (j.n != n) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_by_source: every kind's n must be the chunk's n");
-    in.k[j.kind] = sdxr::KindIn{j.desc_dev, j.rec_dev, j.heap_dev};
-  }
+    return bad_arg(FN, "scratch_dev and state_dev must be 16-byte, times_dev 8-byte, source_dev 4-byte aligned");
+  if (int rc = parse_kinds(FN, kinds, k, n, in)) return rc;
   if (n == 0) return SDX_OK;
-  const int S = n_sources;
-  const int64_t window = times_dev ? window_us : 0;
-  uint8_t* s = static_cast<uint8_t*>(scratch_dev);
-  auto part = [&](int p) { return s + sdx_rs_off(n, S, p); };
-  int32_t* head = reinterpret_cast<int32_t*>(part(SDX_RS_HEAD));
-  sdx_repeat_source_entry* table = reinterpret_cast<sdx_repeat_source_entry*>(part(SDX_RS_TABLE));
-  int32_t* run_lo = reinterpret_cast<int32_t*>(part(SDX_RS_RUN_LO));
-  int32_t* run_hi = reinterpret_cast<int32_t*>(part(SDX_RS_RUN_HI));
-  sdx_repeat_key* lkeys = reinterpret_cast<sdx_repeat_key*>(part(SDX_RS_LKEYS));
-  sdx_repeat_key* keys = reinterpret_cast<sdx_repeat_key*>(part(SDX_RS_KEYS));
-  int64_t* te = reinterpret_cast<int64_t*>(part(SDX_RS_TE));
-  int64_t* ptimes = reinterpret_cast<int64_t*>(part(SDX_RS_PTIMES));
-  int32_t* seg = reinterpret_cast<int32_t*>(part(SDX_RS_SEG));
-  int32_t* succ = reinterpret_cast<int32_t*>(part(SDX_RS_SUCC));
-  int32_t* exitv = reinterpret_cast<int32_t*>(part(SDX_RS_EXIT));
-  int32_t* lastv = reinterpret_cast<int32_t*>(part(SDX_RS_LAST));
-  int32_t* ipred = reinterpret_cast<int32_t*>(part(SDX_RS_IPRED));
-  int32_t* perm = reinterpret_cast<int32_t*>(part(SDX_RS_PERM));
-  uint32_t* k0 = reinterpret_cast<uint32_t*>(part(SDX_RS_K0));
-  uint32_t* k1 = reinterpret_cast<uint32_t*>(part(SDX_RS_K1));
-  int32_t* v0 = reinterpret_cast<int32_t*>(part(SDX_RS_V0));
-  const int nt = (int)sdx_repeat_tiles(n);
-  int32_t* tiles = reinterpret_cast<int32_t*>(part(SDX_RS_TILES));
-  int32_t *tile_last = tiles, *tile_prev = tiles + nt, *tile_head = tiles + 2 * nt, *tile_prevhead = tiles + 3 * nt,
-          *tile_arr = tiles + 4 * nt, *tile_spare = tiles + 5 * nt;
-  uint32_t* hist = reinterpret_cast<uint32_t*>(part(SDX_RS_HIST));
-  uint32_t* tot = reinterpret_cast<uint32_t*>(part(SDX_RS_TOT));
-  uint8_t* flags = part(SDX_RS_FLAGS);
-  uint8_t* state = static_cast<uint8_t*>(state_dev);
+  const int S = n_sources, nt = (int)sdx_repeat_tiles(n);
+  uint8_t *s = static_cast<uint8_t*>(scratch_dev), *state = static_cast<uint8_t*>(state_dev);
+  const TimedBufs b = source_bufs(s, n, S);  // by position; the rest of the scratch: the sort and the runs
+  int32_t *run_lo = part<int32_t>(s, n, S, SDX_RS_RUN_LO), *run_hi = part<int32_t>(s, n, S, SDX_RS_RUN_HI);
+  sdx_repeat_key* lkeys = part<sdx_repeat_key>(s, n, S, SDX_RS_LKEYS);
+  int64_t* ptimes = part<int64_t>(s, n, S, SDX_RS_PTIMES);
+  int32_t *ipred = part<int32_t>(s, n, S, SDX_RS_IPRED), *perm = part<int32_t>(s, n, S, SDX_RS_PERM);
+  uint32_t *k0 = part<uint32_t>(s, n, S, SDX_RS_K0), *k1 = part<uint32_t>(s, n, S, SDX_RS_K1);
+  int32_t* v0 = part<int32_t>(s, n, S, SDX_RS_V0);
+  int32_t* tile_spare = part<int32_t>(s, n, S, SDX_RS_TILES) + 5 * (size_t)nt;
+  uint32_t *hist = part<uint32_t>(s, n, S, SDX_RS_HIST), *tot = part<uint32_t>(s, n, S, SDX_RS_TOT);
   hipStream_t st = (hipStream_t)hip_stream;
-  const dim3 grid(nt), blk(sdxr::T);
-  hipLaunchKernelGGL(sdxr::k_rep_keys, grid, blk, 0, st, in, (int)n, lkeys, tile_spare);
-  const int gi = ((n > S ? n : S) + sdxr::T - 1) / sdxr::T;
+  const dim3 grid(nt), blk(T);
+  hipLaunchKernelGGL(k_rep_keys, grid, blk, 0, st, in, (int)n, lkeys, tile_spare);
+  const int gi = ((n > S ? n : S) + T - 1) / T;
   hipLaunchKernelGGL(sdxs::k_reps_ids, dim3(gi), blk, 0, st, (int)n, S, source_dev, k0, run_lo, run_hi);
   const int passes = sdx_rs_passes(S);
   uint32_t* psrc = k1;
   for (int d = 0; d < passes; ++d) {  // (k0, line) -> (k1, v0 or perm) -> (k0, perm)
     uint32_t *kin = d ? k1 : k0, *kout = d ? k0 : k1;
     hipLaunchKernelGGL(sdxs::k_reps_hist, grid, blk, 0, st, (const uint32_t*)kin, (int)n, nt, d, hist);
-    hipLaunchKernelGGL(sdxs::k_reps_scan, dim3(256 / sdxr::WAVES), blk, 0, st, hist, nt, tot);
+    hipLaunchKernelGGL(sdxs::k_reps_scan, dim3(256 / WAVES), blk, 0, st, hist, nt, tot);
     hipLaunchKernelGGL(sdxs::k_reps_scatter, grid, blk, 0, st, (const uint32_t*)kin, (const int32_t*)(d ? v0 : nullptr),
                        (int)n, nt, d, (const uint32_t*)hist, (const uint32_t*)tot, kout, d == passes - 1 ? perm : v0);
     psrc = kout;
   }
   hipLaunchKernelGGL(sdxs::k_reps_gather, grid, blk, 0, st, (int)n, S, (const int32_t*)perm, (const uint32_t*)psrc,
-                     source_dev, (const sdx_repeat_key*)lkeys, times_dev, keys, ptimes, run_lo, run_hi, tile_last);
-  const sdxt::BySrc bs{psrc, perm, ipred, S};
-  hipLaunchKernelGGL(sdxr::k_rep_tiles, dim3(1), dim3(sdxr::ST), 0, st, (const int32_t*)tile_last, nt, tile_prev, head);
-  hipLaunchKernelGGL(sdxt::k_rept_heads<true>, grid, blk, 0, st, in, (int)n, (const sdx_repeat_key*)keys,
-                     (const int32_t*)tile_prev, (const int64_t*)ptimes, window, (const uint8_t*)state, te, flags, tile_head,
-                     tile_arr, bs);
-  hipLaunchKernelGGL(sdxr::k_rep_tiles, dim3(1), dim3(sdxr::ST), 0, st, (const int32_t*)tile_head, nt, tile_prevhead,
-                     head + 1);
-  hipLaunchKernelGGL(sdxt::k_rept_seg, grid, blk, 0, st, (int)n, (const uint8_t*)flags, (const int32_t*)tile_prevhead, seg);
-  hipLaunchKernelGGL(sdxt::k_rept_succ<true>, grid, blk, 0, st, (int)n, (const int64_t*)te, (const int32_t*)seg,
-                     (const uint8_t*)flags, window, (const uint8_t*)state, succ, exitv, lastv, bs);
-  hipLaunchKernelGGL(sdxt::k_rept_chain<true>, dim3(1), dim3(sdxr::ST), 0, st, in, (int)n, nt, (const sdx_repeat_key*)keys,
-                     (const int32_t*)head, (const int32_t*)tile_head, (const int32_t*)exitv, (const int32_t*)lastv,
-                     (const int64_t*)te, (const uint8_t*)flags, tile_arr, state);
-  hipLaunchKernelGGL(sdxt::k_rept_mark<true>, grid, blk, 0, st, (int)n, (const int32_t*)succ, (const uint8_t*)flags,
-                     (const int32_t*)tile_arr, repeat_dev, bs);
-  hipLaunchKernelGGL(sdxs::k_reps_state, dim3((S + sdxr::WAVES - 1) / sdxr::WAVES), blk, 0, st, in, (int)n, nt, S,
-                     (const sdx_repeat_key*)keys, (const int32_t*)run_lo, (const int32_t*)run_hi, (const int32_t*)ipred,
-                     (const int32_t*)seg, (const int32_t*)exitv, (const int32_t*)lastv, (const int64_t*)te,
-                     (const uint8_t*)flags, (const int32_t*)perm, state, table);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return sdx::set_error(SDX_EHIP, std::string("sdx_mark_repeats_by_source: ") + hipGetErrorString(e));
-  return SDX_OK;
-}
-
-extern "C" size_t sdx_repeat_timed_state_bytes(void) { return sdx_repeat_timed_state_size(); }
-extern "C" size_t sdx_repeat_timed_scratch_bytes(int32_t n) { return sdx_repeat_timed_scratch_size(n); }
-
-extern "C" int sdx_mark_repeats_timed(const sdx_bank* bank, const sdx_json_in* kinds, int k, int32_t n,
-                                      const int64_t* times_dev, int64_t window_us, uint8_t* repeat_dev,
-                                      void* scratch_dev, void* state_dev, void* hip_stream) {
-  namespace sdxt = sdxr::sdxt;
-  (void)bank;
-  if (!kinds || k < 1 || k > 4) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_timed: 1 to 4 kinds");
-  if (n < 0) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_timed: n < 0");
-  if (window_us < 0) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_timed: window_us < 0");
-  if (!times_dev || !repeat_dev || !scratch_dev || !state_dev)
-    return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_timed: null buffer");
-  if ((((uintptr_t)scratch_dev | (uintptr_t)state_dev) & 15) || ((uintptr_t)times_dev & 7))
-    return sdx::set_error(SDX_EINVAL,
-                          "sdx_mark_repeats_timed: scratch_dev and state_dev must be 16-byte, times_dev 8-byte aligned");
-  sdxr::Kinds in{};
-  for (int i = 0; i < k; ++i) {
-    const sdx_json_in& j = kinds[i];
-    if (j.kind < SDX_KIND_MU || j.kind > SDX_KIND_MN)
-      return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_timed: bad kind");
-    if (in.k[j.kind].desc) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_timed: a kind given twice");
-    if (!j.desc_dev || !j.rec_dev || !j.heap_dev)
-      return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_timed: null buffer");
-    if (j.n != n) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats_timed: every kind's n must be the chunk's n");
-    in.k[j.kind] = sdxr::KindIn{j.desc_dev, j.rec_dev, j.heap_dev};
-  }
-  if (n == 0) return SDX_OK;
-  uint8_t* s = static_cast<uint8_t*>(scratch_dev);
-  int32_t* head = reinterpret_cast<int32_t*>(s);
-  sdx_repeat_key* keys = reinterpret_cast<sdx_repeat_key*>(s + sdx_rt_keys_off());
-  int64_t* te = reinterpret_cast<int64_t*>(s + sdx_rt_te_off(n));
-  int32_t* seg = reinterpret_cast<int32_t*>(s + sdx_rt_seg_off(n));
-  int32_t* succ = reinterpret_cast<int32_t*>(s + sdx_rt_succ_off(n));
-  int32_t* exitv = reinterpret_cast<int32_t*>(s + sdx_rt_exit_off(n));
-  int32_t* lastv = reinterpret_cast<int32_t*>(s + sdx_rt_last_off(n));
-  int32_t* tile_last = reinterpret_cast<int32_t*>(s + sdx_rt_tile_off(n, 0));
-  int32_t* tile_prev = reinterpret_cast<int32_t*>(s + sdx_rt_tile_off(n, 1));
-  int32_t* tile_head = reinterpret_cast<int32_t*>(s + sdx_rt_tile_off(n, 2));
-  int32_t* tile_prevhead = reinterpret_cast<int32_t*>(s + sdx_rt_tile_off(n, 3));
-  int32_t* tile_arr = reinterpret_cast<int32_t*>(s + sdx_rt_tile_off(n, 4));
-  uint8_t* flags = s + sdx_rt_flags_off(n);
-  uint8_t* state = static_cast<uint8_t*>(state_dev);
-  const int nt = (int)sdx_repeat_tiles(n);
-  hipStream_t st = (hipStream_t)hip_stream;
-  hipLaunchKernelGGL(sdxr::k_rep_keys, dim3(nt), dim3(sdxr::T), 0, st, in, (int)n, keys, tile_last);
-  hipLaunchKernelGGL(sdxr::k_rep_tiles, dim3(1), dim3(sdxr::ST), 0, st, (const int32_t*)tile_last, nt, tile_prev, head);
-  hipLaunchKernelGGL(sdxt::k_rept_heads<false>, dim3(nt), dim3(sdxr::T), 0, st, in, (int)n, (const sdx_repeat_key*)keys,
-                     (const int32_t*)tile_prev, times_dev, window_us, (const uint8_t*)state, te, flags, tile_head,
-                     tile_arr, sdxt::BySrc{});
-  hipLaunchKernelGGL(sdxr::k_rep_tiles, dim3(1), dim3(sdxr::ST), 0, st, (const int32_t*)tile_head, nt, tile_prevhead,
-                     head + 1);
-  hipLaunchKernelGGL(sdxt::k_rept_seg, dim3(nt), dim3(sdxr::T), 0, st, (int)n, (const uint8_t*)flags,
-                     (const int32_t*)tile_prevhead, seg);
-  hipLaunchKernelGGL(sdxt::k_rept_succ<false>, dim3(nt), dim3(sdxr::T), 0, st, (int)n, (const int64_t*)te, (const int32_t*)seg,
-                     (const uint8_t*)flags, window_us, (const uint8_t*)state, succ, exitv, lastv, sdxt::BySrc{});
-  hipLaunchKernelGGL(sdxt::k_rept_chain<false>, dim3(1), dim3(sdxr::ST), 0, st, in, (int)n, nt, (const sdx_repeat_key*)keys,
-                     (const int32_t*)head, (const int32_t*)tile_head, (const int32_t*)exitv, (const int32_t*)lastv,
-                     (const int64_t*)te, (const uint8_t*)flags, tile_arr, state);
-  hipLaunchKernelGGL(sdxt::k_rept_mark<false>, dim3(nt), dim3(sdxr::T), 0, st, (int)n, (const int32_t*)succ,
-                     (const uint8_t*)flags, (const int32_t*)tile_arr, repeat_dev, sdxt::BySrc{});
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return sdx::set_error(SDX_EHIP, std::string("sdx_mark_repeats_timed: ") + hipGetErrorString(e));
-  return SDX_OK;
-}
-
-extern "C" size_t sdx_repeat_state_bytes(void) { return sdx_repeat_state_size(); }
-extern "C" size_t sdx_repeat_scratch_bytes(int32_t n) { return sdx_repeat_scratch_size(n); }
-extern "C" int sdx_repeat_tile(void) { return SDX_REPEAT_TILE; }
-
-extern "C" int sdx_mark_repeats(const sdx_bank* bank, const sdx_json_in* kinds, int k, int32_t n, uint8_t* repeat_dev,
-                                void* key_scratch_dev, void* state_dev, void* hip_stream) {
-  (void)bank;  // keys are table indices: no bank record is read
-  if (!kinds || k < 1 || k > 4) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats: 1 to 4 kinds");
-  if (n < 0) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats: n < 0");
-  sdxr::Kinds in{};
-  for (int i = 0; i < k; ++i) {
-    const sdx_json_in& j = kinds[i];
-    if (j.kind < SDX_KIND_MU || j.kind > SDX_KIND_MN) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats: bad kind");
-    if (in.k[j.kind].desc) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats: a kind given twice");
-    if (!j.desc_dev || !j.rec_dev || !j.heap_dev) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats: null buffer");
-    if (j.n != n) return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats: every kind's n must be the chunk's n");
-    in.k[j.kind] = sdxr::KindIn{j.desc_dev, j.rec_dev, j.heap_dev};
-  }
-  if (n == 0) return SDX_OK;
-  if (!repeat_dev || !key_scratch_dev || !state_dev)
-    return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats: null buffer");
-  if (((uintptr_t)key_scratch_dev | (uintptr_t)state_dev) & 15)
-    return sdx::set_error(SDX_EINVAL, "sdx_mark_repeats: key_scratch_dev and state_dev must be 16-byte aligned");
-  uint8_t* s = static_cast<uint8_t*>(key_scratch_dev);
-  int32_t* head = reinterpret_cast<int32_t*>(s);
-  sdx_repeat_key* keys = reinterpret_cast<sdx_repeat_key*>(s + sdx_repeat_keys_off());
-  int32_t* tile_last = reinterpret_cast<int32_t*>(s + sdx_repeat_tile_last_off(n));
-  int32_t* tile_prev = reinterpret_cast<int32_t*>(s + sdx_repeat_tile_prev_off(n));
-  const int nt = (int)sdx_repeat_tiles(n);
-  hipStream_t st = (hipStream_t)hip_stream;
-  hipLaunchKernelGGL(sdxr::k_rep_keys, dim3(nt), dim3(sdxr::T), 0, st, in, (int)n, keys, tile_last);
-  hipLaunchKernelGGL(sdxr::k_rep_tiles, dim3(1), dim3(sdxr::ST), 0, st, (const int32_t*)tile_last, nt, tile_prev, head);
-  hipLaunchKernelGGL(sdxr::k_rep_resolve, dim3(nt), dim3(sdxr::T), 0, st, in, (int)n, (const sdx_repeat_key*)keys,
-                     (const int32_t*)tile_prev, (const uint8_t*)state_dev, repeat_dev);
-  hipLaunchKernelGGL(sdxr::k_rep_state, dim3(1), dim3(sdxr::T), 0, st, in, (const sdx_repeat_key*)keys,
-                     (const int32_t*)head, static_cast<uint8_t*>(state_dev));
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return sdx::set_error(SDX_EHIP, std::string("sdx_mark_repeats: ") + hipGetErrorString(e));
-  return SDX_OK;
+                     source_dev, (const sdx_repeat_key*)lkeys, times_dev, b.keys, ptimes, run_lo, run_hi, b.tile_last);
+  // without times every time is 0 and W = 0: no gap ever exceeds the window
+  launch_timed<true>(in, n, b, ptimes, times_dev ? window_us : 0, state, repeat_dev, sdxt::BySrc{psrc, perm, ipred, S}, st);
+  hipLaunchKernelGGL(sdxs::k_reps_state, dim3((S + WAVES - 1) / WAVES), blk, 0, st, in, (int)n, nt, S,
+                     (const sdx_repeat_key*)b.keys, (const int32_t*)run_lo, (const int32_t*)run_hi, (const int32_t*)ipred,
+                     (const int32_t*)b.seg, (const int32_t*)b.exitv, (const int32_t*)b.lastv, (const int64_t*)b.te,
+                     (const uint8_t*)b.flags, (const int32_t*)perm, state,
+                     part<sdx_repeat_source_entry>(s, n, S, SDX_RS_TABLE));
+  return launched(FN);
 }

@@ -638,6 +638,9 @@ class SignalParser:
 
         rep = np.zeros(n, np.uint8)   # the device's repeat mask (collapse)
         if collapse:
+            from .repeats import RepeatPass, apply_mask, count_sources, objects_key, text_key
+            rpass = RepeatPass(eng, window_us, None if sources is None else count_sources(sources))
+            rbufs = None
             # every kind's launch first (their outputs stay on the device), then ONE sdx_mark_repeats over
             # them, then the serialiser with the mask: a repeat is never turned into text
             kept = []
@@ -656,30 +659,14 @@ class SignalParser:
                 else:
                     raise RuntimeError("result capacity overflow persists")
                 kept.append((kind, out, json_cap))
-            table = None
-            if kept and sources is not None:   # one (K, T) per source id
-                from .repeats import count_sources
-                S = count_sources(sources)
-                rep_dev, scratch = eng.alloc_repeat_sources(n, S)
-                eng.mark_repeats_by_source([eng.json_in(kind, out, lo, n) for kind, out, _ in kept], n,
-                                           eng.torch.from_numpy(sources).to(eng.dev), S,
-                                           None if window_us is None else eng.torch.from_numpy(times).to(eng.dev),
-                                           window_us, rep_dev, scratch, eng.alloc_repeat_state(sources=S))
-                table = eng.repeat_sources_table(scratch, S).cpu().numpy().view(runtime.REPEAT_SOURCE_ENTRY)
-            elif kept and window_us is not None:
-                rep_dev, scratch = eng.alloc_repeat_timed(n)
-                times_dev = eng.torch.from_numpy(times).to(eng.dev)
-                eng.mark_repeats_timed([eng.json_in(kind, out, lo, n) for kind, out, _ in kept], n, times_dev, window_us,
-                                       rep_dev, scratch, eng.alloc_repeat_state(timed=True))
-            elif kept:
-                rep_dev, scratch = eng.alloc_repeat(n)
-                eng.mark_repeats([eng.json_in(kind, out, lo, n) for kind, out, _ in kept], n, rep_dev, scratch,
-                                 eng.alloc_repeat_state())
-            if kept:
+            if kept:   # a fresh stream of lines per call; nothing is read back but the mask (and the sources' table)
+                rbufs = rpass.alloc(n, pinned=False)
+                rpass.enqueue(rbufs, [eng.json_in(kind, out, lo, n) for kind, out, _ in kept], n, times=times,
+                              sources=sources)
                 for kind, out, json_cap in kept:
                     for _attempt in range(4):
                         jo = eng.alloc_json(n, json_cap)
-                        eng.launch_json(kind, out, lo, n, jo, first_only=True, skip=rep_dev)
+                        eng.launch_json(kind, out, lo, n, jo, first_only=True, skip=rbufs.mask)
                         c2 = jo["cursor"].cpu().numpy()
                         if not c2[1]:
                             break
@@ -687,7 +674,7 @@ class SignalParser:
                     else:
                         raise RuntimeError("JSON capacity overflow persists")
                     take_texts(jo, c2[0])
-                rep = rep_dev[:n].cpu().numpy()
+                rep = rbufs.mask[:n].cpu().numpy()
             jobs = []
         for kind, rec_cap, heap_cap, json_cap, launches in jobs:
             for _attempt in range(4):
@@ -720,7 +707,6 @@ class SignalParser:
         if grows:  # general-path lines (rare): their objects through parse_lines, the text as _message_to_json
             for i, g in zip(grows, self.parse_lines([lines[i] for i in grows])):
                 if collapse:
-                    from .repeats import objects_key
                     host_keys[i] = objects_key(g)
                 if exact[i]:
                     if isinstance(g, ContractError):
@@ -738,25 +724,22 @@ class SignalParser:
                 texts[i] = ContractError(f"line {i} is outside the device contract of the front end "
                                          f"(kind {_KIND_NAME.get(int(kinds[i]), '?')})")
         if collapse:
-            from .repeats import RepeatTracker, SourceTrackers, text_key
             fetched = {}
 
             def fetch_key(i):   # a flagged line whose run head the host does not know: the batch API
                 fetched[i] = self.parse_lines_json([lines[i]])[0]
                 return text_key(_KIND_NAME[int(kinds[i])], fetched[i]) if isinstance(fetched[i], str) else None
 
-            wkw = {} if window_us is None else {"times": times, "window_us": window_us}
             dev_key_of = lambda i: text_key(_KIND_NAME[int(kinds[i])], texts[i])   # noqa: E731
-            if sources is not None:
-                mask = SourceTrackers().fix_chunk(sources, rep, has_text, dev_key_of, host_keys, fetch_key=fetch_key,
-                                                  table=table, **wkw)
-            else:
-                mask = RepeatTracker().fix_chunk(rep, has_text, dev_key_of, host_keys, fetch_key=fetch_key, **wkw)
-            for i in sorted(set(np.nonzero(mask != rep)[0].tolist()) | set(host_keys)):
-                if mask[i]:
-                    texts[i] = None      # a host-resolved repeat, or a repeat of a host-resolved line
-                elif i not in host_keys and rep[i]:  # the device skipped it, but its predecessor was a host row
-                    texts[i] = fetched[i] if i in fetched else self.parse_lines_json([lines[i]])[0]
+            mask = rpass.exact_mask(rbufs, rep, has_text, dev_key_of, host_keys, fetch=fetch_key, times=times,
+                                    sources=sources)
+
+            def drop(i):         # a host-resolved repeat, or a repeat of a host-resolved line
+                texts[i] = None
+
+            def republish(i):    # the device skipped it, but its predecessor was a host row
+                texts[i] = fetched[i] if i in fetched else self.parse_lines_json([lines[i]])[0]
+            apply_mask(mask, rep, host_keys, drop, republish)
             self.last_repeat_mask = mask
         return texts
 

@@ -1,4 +1,5 @@
-"""Repeat suppression, host side.
+"""Repeat suppression: the definition, the argument checks, the trackers that make the device's
+mask exact around host-resolved rows, and :class:`RepeatPass`, which drives the device pass for stream and front end.
 
 The definition, in line order within one stream of lines (one LineStream, or one parse_lines* /
 parse_bytes* call): a line is RESULT-BEARING when the reference's parse_line returns a non-empty list
@@ -32,9 +33,12 @@ id, device keys by its table index; inside one kind the two correspond one to on
 from __future__ import annotations
 
 import json
+from types import SimpleNamespace
 from typing import Callable, Dict, Iterable, Optional, Tuple
 
 import numpy as np
+
+from . import runtime
 
 Key = Tuple[str, str, str]   # (kind name, protocol_id, payload)
 
@@ -364,3 +368,101 @@ class SourceTrackers:
                                      None if fetch_key is None else (lambda j: fetch_key(at[j])), end_key,
                                      **({} if window_us is None else {"times": t[idx], "window_us": window_us}))
         return mask
+
+
+def apply_mask(mask, rep, host_keys, drop: Callable[[int], None], republish: Callable[[int], None]) -> None:
+    """A chunk's published lines follow the exact ``mask`` where it differs from the device's (``rep``, by which
+    it skipped texts) and on the host rows (``host_keys``): ``drop(i)`` for a repeat that was published -- a host
+    row, or a device line behind one --, ``republish(i)`` for a line the device skipped behind a host row."""
+    for i in sorted(set(np.nonzero(mask != rep)[0].tolist()) | set(host_keys)):
+        if mask[i]:
+            drop(i)
+        elif i not in host_keys and rep[i]:
+            republish(i)
+
+
+STATE_HEAD = 16 + 240   # bytes of the untimed state read back per chunk: its header + a payload of up to 240 bytes
+_KINDS = ("MU", "MS", "MC", "MN")   # enum sdx_kind
+
+
+class RepeatPass:
+    """The device pass of one stream of lines and the tracker that makes its mask exact -- the only place that
+    knows which of the three modes runs: plain (sdx_mark_repeats), ``window_us`` (sdx_mark_repeats_timed),
+    ``n_sources`` with or without a window (sdx_mark_repeats_by_source).  It owns the carried device state
+    (allocated with the first chunk buffers) and the RepeatTracker / SourceTrackers that follow it."""
+
+    def __init__(self, eng, window_us: Optional[int] = None, n_sources: Optional[int] = None):
+        self.eng, self.window_us, self.n_sources = eng, window_us, n_sources
+        self.tracker = SourceTrackers() if n_sources is not None else RepeatTracker()
+        self.state = None
+
+    def alloc(self, cap: int, pinned: bool) -> SimpleNamespace:
+        """The buffers of one chunk of up to ``cap`` lines: ``mask`` (device uint8[cap]) and the mode's ``scratch``.
+        ``pinned``: a stream's slot -- where the mode takes times / ids, device ``d_times`` / ``d_src`` beside
+        their pinned host copies ``h_times`` / ``h_src``, and ``h_read``, the pinned buffer of the chunk's one
+        readback; False: a one-shot call, which hands enqueue its own arrays and reads nothing back."""
+        import torch as t    # here, not at the top: the module is imported where there is no torch
+        eng, S = self.eng, self.n_sources
+        b = SimpleNamespace(d_times=None, d_src=None, h_times=None, h_src=None, h_read=None)
+        if S is not None:
+            b.mask, b.scratch = eng.alloc_repeat_sources(cap, S)
+            read = runtime.REPEAT_SOURCE_ENTRY.itemsize * S    # the compact table: every source's header and last line
+        elif self.window_us is not None:
+            b.mask, b.scratch = eng.alloc_repeat_timed(cap)
+            read = 0    # the tracker follows (K, T) from the mask, the keys and the times
+        else:
+            b.mask, b.scratch = eng.alloc_repeat(cap)
+            read = STATE_HEAD
+        if self.state is None:
+            self.state = (eng.alloc_repeat_state(sources=S) if S is not None else
+                          eng.alloc_repeat_state() if self.window_us is None else eng.alloc_repeat_state(timed=True))
+        if pinned:
+            if S is not None:
+                b.d_src = t.zeros(cap, dtype=t.int32, device=eng.dev)
+                b.h_src = t.zeros(cap, dtype=t.int32).pin_memory()
+            if self.window_us is not None:
+                b.d_times = t.zeros(cap, dtype=t.int64, device=eng.dev)
+                b.h_times = t.zeros(cap, dtype=t.int64).pin_memory()
+            if read:
+                b.h_read = t.zeros(read, dtype=t.uint8).pin_memory()
+        return b
+
+    def enqueue(self, b, json_ins, n: int, stream=None, times=None, sources=None) -> None:
+        """The one Engine.mark_* call on ``stream`` (None: the current one): b.mask[:n] and the carried state;
+        with b.h_read, the one copy behind it.  The times / ids are those in b.d_times / b.d_src (a stream
+        uploads them with the chunk's bytes), or the one-shot call's own host arrays ``times`` / ``sources``."""
+        eng, w = self.eng, self.window_us
+        d_times = b.d_times if times is None or w is None else eng.torch.from_numpy(times).to(eng.dev)
+        if self.n_sources is not None:
+            d_src = b.d_src if sources is None else eng.torch.from_numpy(sources).to(eng.dev)
+            eng.mark_repeats_by_source(json_ins, n, d_src, self.n_sources, d_times, w, b.mask, b.scratch, self.state,
+                                       stream=stream)
+        elif w is not None:
+            eng.mark_repeats_timed(json_ins, n, d_times, w, b.mask, b.scratch, self.state, stream=stream)
+        else:
+            eng.mark_repeats(json_ins, n, b.mask, b.scratch, self.state, stream=stream)
+        if b.h_read is not None:   # the sources' compact table, or the untimed state's head
+            runtime.copy_async(b.h_read, eng.repeat_sources_table(b.scratch, self.n_sources)
+                               if self.n_sources is not None else self.state[:STATE_HEAD], stream)
+
+    def exact_mask(self, b, rep, has_key, dev_key_of, host_keys, redo=(), fetch=None,
+                   times=None, sources=None, bank=None) -> np.ndarray:
+        """The chunk's exact mask from the device's (``rep``, on the host by now): the tracker's fix_chunk (see
+        there for has_key .. fetch) with what the pass read back.  ``b``: the chunk's buffers (None: no pass ran);
+        ``times`` / ``sources``: the chunk's host arrays; ``bank``: names the protocol ids in an untimed state."""
+        wkw = {} if self.window_us is None else {"times": times, "window_us": self.window_us}
+        if self.n_sources is not None:
+            table = None
+            if b is not None:   # a stream's copy, or a one-shot call's read now
+                raw = b.h_read if b.h_read is not None else self.eng.repeat_sources_table(b.scratch, self.n_sources).cpu()
+                table = raw.numpy().view(runtime.REPEAT_SOURCE_ENTRY)
+            return self.tracker.fix_chunk(sources, rep, has_key, dev_key_of, host_keys, redo, fetch, table=table, **wkw)
+        end_key = None
+        if self.window_us is None and b is not None and b.h_read is not None:
+            # what the device's state held after this chunk (read back behind its state pass)
+            hs = b.h_read.numpy()
+            valid, kd, proto, ln = (int(x) for x in hs[:16].view(np.uint32))
+            if valid and ln <= STATE_HEAD - 16:
+                pids = (bank.mu_pids, bank.ms_pids, bank.mc_pids, bank.mn_pids)[kd]
+                end_key = (_KINDS[kd], str(pids[proto]), hs[16: 16 + ln].tobytes().decode("latin-1"))
+        return self.tracker.fix_chunk(rep, has_key, dev_key_of, host_keys, redo, fetch, end_key, **wkw)

@@ -740,33 +740,38 @@ class Engine:
             size = self.lib.sdx_repeat_timed_state_bytes() if timed else self.lib.sdx_repeat_state_bytes()
         return t.zeros(int(size), dtype=t.uint8, device=self.dev)
 
+    def _alloc_repeat(self, n: int, scratch_bytes: int):
+        t = self.torch
+        return (t.zeros(max(n, 1), dtype=t.uint8, device=self.dev), t.empty(int(scratch_bytes), dtype=t.uint8, device=self.dev))
+
+    def _mark(self, name: str, entry, json_ins, n: int, sizes, args, stream, too_small: str = "n") -> None:
+        """What the three mark_* methods share.  ``sizes``: (tensor or None, the bytes it must hold) per buffer;
+        ``args``: the entry's arguments between n and the stream."""
+        if not 1 <= len(json_ins) <= 4:
+            raise ValueError(f"{name}: 1 to 4 kinds")
+        for x, need in sizes:
+            if x is not None and x.numel() * x.element_size() < need:
+                raise ValueError(f"{name}: a buffer is too small for {too_small}")
+        arr = (SdxJsonIn * len(json_ins))(*json_ins)
+        st = self.stream_ptr() if stream is None else c_void_p(stream.cuda_stream)
+        _check(self.lib, entry(self.handle, arr, len(json_ins), n, *args, st))
+
     def alloc_repeat(self, n: int):
         """(repeat mask uint8[n], key scratch) for chunks of up to n lines."""
-        t = self.torch
-        return (t.zeros(max(n, 1), dtype=t.uint8, device=self.dev),
-                t.empty(int(self.lib.sdx_repeat_scratch_bytes(max(n, 1))), dtype=t.uint8, device=self.dev))
+        return self._alloc_repeat(n, self.lib.sdx_repeat_scratch_bytes(max(n, 1)))
 
     def mark_repeats(self, json_ins, n: int, repeat, scratch, state, stream=None) -> None:
         """sdx_mark_repeats on ``stream`` (default: the current one; no host sync): repeat[:n] = 1 for the
         lines that repeat the previous result-bearing line's (kind, proto, payload).  ``json_ins``: the
         chunk's SdxJsonIn, one per kind (json_in); ``state``: alloc_repeat_state() of this stream of lines."""
-        n = int(n)
-        if not 1 <= len(json_ins) <= 4:
-            raise ValueError("mark_repeats: 1 to 4 kinds")
-        if (repeat.numel() * repeat.element_size() < n or
-                scratch.numel() * scratch.element_size() < int(self.lib.sdx_repeat_scratch_bytes(n)) or
-                state.numel() * state.element_size() < int(self.lib.sdx_repeat_state_bytes())):
-            raise ValueError("mark_repeats: a buffer is too small for n")
-        arr = (SdxJsonIn * len(json_ins))(*json_ins)
-        st = self.stream_ptr() if stream is None else c_void_p(stream.cuda_stream)
-        _check(self.lib, self.lib.sdx_mark_repeats(self.handle, arr, len(json_ins), n, _ptr(repeat), _ptr(scratch),
-                                                   _ptr(state), st))
+        n, lib = int(n), self.lib
+        self._mark("mark_repeats", lib.sdx_mark_repeats, json_ins, n,
+                   [(repeat, n), (scratch, lib.sdx_repeat_scratch_bytes(n)), (state, lib.sdx_repeat_state_bytes())],
+                   (_ptr(repeat), _ptr(scratch), _ptr(state)), stream)
 
     def alloc_repeat_timed(self, n: int):
         """(repeat mask uint8[n], scratch) of mark_repeats_timed for chunks of up to n lines."""
-        t = self.torch
-        return (t.zeros(max(n, 1), dtype=t.uint8, device=self.dev),
-                t.empty(int(self.lib.sdx_repeat_timed_scratch_bytes(max(n, 1))), dtype=t.uint8, device=self.dev))
+        return self._alloc_repeat(n, self.lib.sdx_repeat_timed_scratch_bytes(max(n, 1)))
 
     def mark_repeats_timed(self, json_ins, n: int, times, window_us: int, repeat, scratch, state, stream=None) -> None:
         """sdx_mark_repeats_timed on ``stream`` (default: the current one; no host sync): mark_repeats where a
@@ -774,24 +779,15 @@ class Engine:
         int64 tensor, one arrival time in microseconds per line, non-decreasing (a precondition the caller
         checks: frontend / stream do); ``scratch``: alloc_repeat_timed's; ``state``:
         alloc_repeat_state(timed=True) of this stream of lines."""
-        n = int(n)
-        if not 1 <= len(json_ins) <= 4:
-            raise ValueError("mark_repeats_timed: 1 to 4 kinds")
-        if (repeat.numel() * repeat.element_size() < n or
-                (times is not None and times.numel() * times.element_size() < 8 * n) or
-                scratch.numel() * scratch.element_size() < int(self.lib.sdx_repeat_timed_scratch_bytes(n)) or
-                state.numel() * state.element_size() < int(self.lib.sdx_repeat_timed_state_bytes())):
-            raise ValueError("mark_repeats_timed: a buffer is too small for n")
-        arr = (SdxJsonIn * len(json_ins))(*json_ins)
-        st = self.stream_ptr() if stream is None else c_void_p(stream.cuda_stream)
-        _check(self.lib, self.lib.sdx_mark_repeats_timed(self.handle, arr, len(json_ins), n, _ptr(times), int(window_us),
-                                                         _ptr(repeat), _ptr(scratch), _ptr(state), st))
+        n, lib = int(n), self.lib
+        self._mark("mark_repeats_timed", lib.sdx_mark_repeats_timed, json_ins, n,
+                   [(repeat, n), (times, 8 * n), (scratch, lib.sdx_repeat_timed_scratch_bytes(n)),
+                    (state, lib.sdx_repeat_timed_state_bytes())],
+                   (_ptr(times), int(window_us), _ptr(repeat), _ptr(scratch), _ptr(state)), stream)
 
     def alloc_repeat_sources(self, n: int, sources: int):
         """(repeat mask uint8[n], scratch) of mark_repeats_by_source for chunks of up to n lines of ``sources`` ids."""
-        t = self.torch
-        size = self.lib.sdx_repeat_sources_scratch_bytes(max(n, 1), _n_sources(sources))
-        return (t.zeros(max(n, 1), dtype=t.uint8, device=self.dev), t.empty(int(size), dtype=t.uint8, device=self.dev))
+        return self._alloc_repeat(n, self.lib.sdx_repeat_sources_scratch_bytes(max(n, 1), _n_sources(sources)))
 
     def mark_repeats_by_source(self, json_ins, n: int, source, sources: int, times, window_us, repeat, scratch, state,
                                stream=None) -> None:
@@ -800,21 +796,13 @@ class Engine:
         [0, sources) per line; ``times`` / ``window_us``: as mark_repeats_timed, non-decreasing within each
         source, or None / None for no window (both preconditions are the caller's: frontend / stream check
         them); ``scratch``: alloc_repeat_sources(n, sources)'s; ``state``: alloc_repeat_state(sources=)."""
-        n = int(n)
-        if not 1 <= len(json_ins) <= 4:
-            raise ValueError("mark_repeats_by_source: 1 to 4 kinds")
-        size = lambda x: x.numel() * x.element_size()   # noqa: E731
-        if 1 <= sources <= REPEAT_SOURCES_MAX and (
-                size(repeat) < n or (source is not None and size(source) < 4 * n) or
-                (times is not None and size(times) < 8 * n) or
-                size(scratch) < int(self.lib.sdx_repeat_sources_scratch_bytes(n, sources)) or
-                size(state) < int(self.lib.sdx_repeat_sources_state_bytes(sources))):
-            raise ValueError("mark_repeats_by_source: a buffer is too small for n and sources")
-        arr = (SdxJsonIn * len(json_ins))(*json_ins)
-        st = self.stream_ptr() if stream is None else c_void_p(stream.cuda_stream)
-        _check(self.lib, self.lib.sdx_mark_repeats_by_source(
-            self.handle, arr, len(json_ins), n, _ptr(source), int(sources), _ptr(times),
-            0 if window_us is None else int(window_us), _ptr(repeat), _ptr(scratch), _ptr(state), st))
+        n, lib = int(n), self.lib
+        ok = 1 <= sources <= REPEAT_SOURCES_MAX    # otherwise the entry refuses the count itself
+        self._mark("mark_repeats_by_source", lib.sdx_mark_repeats_by_source, json_ins, n,
+                   [(repeat, n), (source, 4 * n), (times, 8 * n), (scratch, lib.sdx_repeat_sources_scratch_bytes(n, sources)),
+                    (state, lib.sdx_repeat_sources_state_bytes(sources))] if ok else [],
+                   (_ptr(source), int(sources), _ptr(times), 0 if window_us is None else int(window_us), _ptr(repeat),
+                    _ptr(scratch), _ptr(state)), stream, "n and sources")
 
     def repeat_sources_table(self, scratch, sources: int):
         """The compact per-source table mark_repeats_by_source left in ``scratch``: a device uint8 view

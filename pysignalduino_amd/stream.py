@@ -50,7 +50,6 @@ _KINDS = (("MU", runtime.KIND_MU, runtime.SEL_MU_SHORT, runtime.SEL_MU_LONG),
 _FUSE = os.environ.get("SDX_STREAM_FUSE", "1") != "0"
 _GROUP2 = os.environ.get("SDX_STREAM_GROUP2", "1") != "0"   # A/B: one sdx_group_step vs two groupings
 _MC_SEP = os.environ.get("SDX_STREAM_MC_SEP") == "1"   # A/B: MC's short class in its own launch
-_STATE_HEAD = 16 + 240   # bytes of the repeat state read back per chunk: its header + a payload of up to 240 bytes
 
 
 class _NlView:
@@ -280,21 +279,9 @@ class _Slot:
             self.h_sizes = t.zeros(runtime.XCHG_COUNTS * len(self.outs) + 4 * len(self.outs), dtype=t.int32).pin_memory()
             cap = sum(16 * C + 8 * o["rec_cap"] + o["heap_cap"] + 64 for o in self.outs.values())
             self.h_out = t.empty(cap + 3 * C + 64, dtype=t.uint8).pin_memory()
-        if ls.collapse and ls.n_sources is not None:   # the by-source pass: the chunk's ids, the compact table read back
-            self.rep, self.rep_scratch = eng.alloc_repeat_sources(C, ls.n_sources)
-            self.d_src = t.zeros(C, dtype=t.int32, device=eng.dev)
-            self.h_src = t.zeros(C, dtype=t.int32).pin_memory()
-            self.h_table = t.zeros(runtime.REPEAT_SOURCE_ENTRY.itemsize * ls.n_sources, dtype=t.uint8).pin_memory()
-            if ls.window_us is not None:
-                self.d_times = t.zeros(C, dtype=t.int64, device=eng.dev)
-                self.h_times = t.zeros(C, dtype=t.int64).pin_memory()
-        elif ls.collapse and ls.window_us is not None:   # the timed pass: its scratch, the chunk's arrival times
-            self.rep, self.rep_scratch = eng.alloc_repeat_timed(C)
-            self.d_times = t.zeros(C, dtype=t.int64, device=eng.dev)
-            self.h_times = t.zeros(C, dtype=t.int64).pin_memory()
-        elif ls.collapse:   # the repeat mask, sdx_mark_repeats' scratch, and the state's head read back per chunk
-            self.rep, self.rep_scratch = eng.alloc_repeat(C)
-            self.h_state = t.zeros(_STATE_HEAD, dtype=t.uint8).pin_memory()
+        if ls.collapse:   # the repeat pass's buffers: the mask, and the pinned copies the chunk's times / ids go through
+            self.rb = ls.repeats.alloc(C, pinned=True)
+            self.rep, self.h_times, self.h_src = self.rb.mask, self.rb.h_times, self.rb.h_src
         self.reset()
 
     def reset(self):
@@ -355,14 +342,11 @@ class LineStream:
         self.B = int(chunk_bytes or 256 * self.C)
         self.lag = max(1, int(lag))
         if self.collapse:
-            # repeat suppression: ONE state per stream, written by every chunk's state pass;
-            # rep_ev orders the next chunk's sdx_mark_repeats (on the other demodulation stream) behind it
-            from .repeats import RepeatTracker, SourceTrackers
-            self.rep_state = (self.eng.alloc_repeat_state(sources=self.n_sources) if self.n_sources is not None else
-                              self.eng.alloc_repeat_state() if self.window_us is None else
-                              self.eng.alloc_repeat_state(timed=True))
+            # repeat suppression: ONE state per stream (the RepeatPass's), written by every chunk's
+            # state pass; rep_ev orders the next chunk's pass (on the other demodulation stream) behind it
+            from .repeats import RepeatPass
+            self.repeats = RepeatPass(self.eng, self.window_us, self.n_sources)
             self.rep_ev = None
-            self.tracker = SourceTrackers() if self.n_sources is not None else RepeatTracker()
         self.slots = [_Slot(self) for _ in range(self.lag + 1)]
         dev = self.eng.dev
         # the parse at the highest priority: the host waits for chunk k's class counts before it can
@@ -466,10 +450,10 @@ class LineStream:
     def _upload_times(self, s: _Slot) -> None:
         """On the input stream, in front of the chunk's h2d event: 8 bytes per line, 4 for its source id."""
         if s.times is not None and s.n:
-            runtime.copy_async(s.d_times[: s.n], s.h_times[: s.n], self.cin)
+            runtime.copy_async(s.rb.d_times[: s.n], s.h_times[: s.n], self.cin)
             self.h2d_bytes += 8 * s.n
         if s.sources is not None and s.n:
-            runtime.copy_async(s.d_src[: s.n], s.h_src[: s.n], self.cin)
+            runtime.copy_async(s.rb.d_src[: s.n], s.h_src[: s.n], self.cin)
             self.h2d_bytes += 4 * s.n
 
     def _queued(self, s: _Slot) -> int:
@@ -761,18 +745,8 @@ class LineStream:
                 if self.rep_ev is not None:
                     sd.wait_event(self.rep_ev)
                 ins = [eng.json_in(kd, s.outs[name], lo, n, 2) for name, kd, _, _ in _KINDS if name in s.outs]
-                if self.n_sources is not None:   # the ids (and times) came up with the chunk's bytes; the compact
-                    # table back in one copy: every source's header and last result-bearing line
-                    eng.mark_repeats_by_source(ins, n, s.d_src, self.n_sources,
-                                               None if self.window_us is None else s.d_times, self.window_us, s.rep,
-                                               s.rep_scratch, self.rep_state, stream=sd)
-                    runtime.copy_async(s.h_table, eng.repeat_sources_table(s.rep_scratch, self.n_sources), sd)
-                elif self.window_us is None:
-                    eng.mark_repeats(ins, n, s.rep, s.rep_scratch, self.rep_state, stream=sd)
-                    runtime.copy_async(s.h_state, self.rep_state[:_STATE_HEAD], sd)
-                else:   # the chunk's times came up with its bytes (stage A, in front of the parse)
-                    eng.mark_repeats_timed(ins, n, s.d_times, self.window_us, s.rep, s.rep_scratch, self.rep_state,
-                                           stream=sd)
+                # the chunk's times and ids came up with its bytes (stage A, in front of the parse)
+                self.repeats.enqueue(s.rb, ins, n, sd)
                 self.rep_ev = t.cuda.Event()
                 self.rep_ev.record(sd)
             if self.output == "json":
@@ -838,8 +812,7 @@ class LineStream:
             s.kb = b
             if self.collapse:
                 runtime.copy_async(ho[b + 2 * n: b + 3 * n], s.rep[:n], self.cout)
-                self.d2h_bytes += n + (s.h_table.numel() if self.n_sources is not None else
-                                       _STATE_HEAD if self.window_us is None else 0)
+                self.d2h_bytes += n + (s.rb.h_read.numel() if s.rb.h_read is not None else 0)
             if s.src is not None:   # a submit_bytes chunk: the offsets the device found, for line(i)
                 runtime.copy_async(s.h_offs[: n + 1], lb.offsets[: n + 1], self.cout)
                 self.d2h_bytes += 8 * (n + 1)
@@ -902,7 +875,7 @@ class LineStream:
     def _fix_repeats(self, s: _Slot, r: ChunkResult, rep: np.ndarray, redo_kinds, kname) -> None:
         """r.repeat = the chunk's exact mask: the device's, re-decided around the host-resolved rows
         (repeats.RepeatTracker); texts and host results follow it."""
-        from .repeats import objects_key, text_key
+        from .repeats import apply_mask, objects_key, text_key
         n, kind, js = r.n, r.kind, self.output == "json"
         name_of = lambda i: kname.get(int(kind[i]), "?")   # noqa: E731
         host_keys = {i: ((text_key(name_of(i), x) if isinstance(x, str) else None) if js else objects_key(x))
@@ -924,41 +897,22 @@ class LineStream:
                 return text_key(name_of(i), bytes(blob[o: o + int(r.len[i])]).decode("ascii"))
         else:
             has_key, dev_key_of = self._wire_keys(r)
-        if self.n_sources is not None:   # one tracker per source, over the source's lines of the chunk
+        if s.sources is not None:
             r.source = s.sources.copy()
-            mask = self.tracker.fix_chunk(r.source, rep, has_key, dev_key_of, host_keys, redo, fetch,
-                                          table=s.h_table.numpy().view(runtime.REPEAT_SOURCE_ENTRY),
-                                          **({} if self.window_us is None else
-                                             {"times": s.times, "window_us": self.window_us}))
-            self._apply_mask(s, r, rep, mask, host_keys, fetched)
+        r.repeat = mask = self.repeats.exact_mask(s.rb, rep, has_key, dev_key_of, host_keys, redo, fetch,
+                                                  times=s.times, sources=r.source, bank=self.bank)
+        if not js:
             return
-        if self.window_us is not None:   # the tracker follows (K, T) from the mask, the keys and the times
-            mask = self.tracker.fix_chunk(rep, has_key, dev_key_of, host_keys, redo, fetch, times=s.times,
-                                          window_us=self.window_us)
-            self._apply_mask(s, r, rep, mask, host_keys, fetched)
-            return
-        # what the device's state held after this chunk (read back behind its state pass)
-        hs = s.h_state.numpy()
-        valid, kd, proto, ln = (int(x) for x in hs[:16].view(np.uint32))
-        end_key = None
-        if valid and ln <= _STATE_HEAD - 16:
-            pids = (self.bank.mu_pids, self.bank.ms_pids, self.bank.mc_pids, self.bank.mn_pids)[kd]
-            end_key = (("MU", "MS", "MC", "MN")[kd], str(pids[proto]), hs[16: 16 + ln].tobytes().decode("latin-1"))
-        mask = self.tracker.fix_chunk(rep, has_key, dev_key_of, host_keys, redo, fetch, end_key)
-        self._apply_mask(s, r, rep, mask, host_keys, fetched)
 
-    def _apply_mask(self, s: _Slot, r: ChunkResult, rep, mask, host_keys, fetched) -> None:
-        r.repeat = mask
-        if self.output != "json":
-            return
-        for i in sorted(set(np.nonzero(mask != rep)[0].tolist()) | set(host_keys)):
-            if mask[i]:
-                if i in r.host:
-                    r.host[i] = None
-                else:
-                    r.len[i] = 0           # a repeat of a host-resolved line: its text is not published
-            elif i not in host_keys and rep[i]:   # skipped on the device, but its predecessor was a host row
-                r.host[i] = fetched[i] if i in fetched else self.parser.parse_lines_json([self._line(s, i)])[0]
+        def drop(i):
+            if i in r.host:
+                r.host[i] = None
+            else:
+                r.len[i] = 0           # a repeat of a host-resolved line: its text is not published
+
+        def republish(i):              # skipped on the device, but its predecessor was a host row
+            r.host[i] = fetched[i] if i in fetched else self.parser.parse_lines_json([self._line(s, i)])[0]
+        apply_mask(mask, rep, host_keys, drop, republish)
 
     def _wire_keys(self, r: ChunkResult):
         """wire output: (which lines have results, line -> key) from the chunk's wire sections; the

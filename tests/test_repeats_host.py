@@ -134,6 +134,26 @@ def test_collapse_objects_is_the_definition():
     assert out[2] == [] and out[5] == [] and out[0] and isinstance(out[3], ValueError)
 
 
+def test_apply_mask_drops_and_republishes():
+    """Lines 0 A (device), 1 G (host row), 2 A (device), 3 G (host row), 4 G (device), 5 A, 6 A (device).
+    The device does not see the host rows: it skipped line 2 as a repeat of line 0 -- its true predecessor
+    is the host row 1, so it is published after all -- and published line 4, which repeats the host row 3;
+    line 3 is no repeat, lines 5 and 6 were decided correctly."""
+    rep = np.array([0, 0, 1, 0, 0, 0, 1], np.uint8)      # the device's mask
+    mask = np.array([0, 0, 0, 0, 1, 0, 1], np.uint8)     # the exact one
+    dropped, republished = [], []
+    repeats.apply_mask(mask, rep, {1: ("MU", "9", "gg"), 3: ("MU", "9", "gg")}, dropped.append, republished.append)
+    assert republished == [2] and dropped == [4]
+    # a host row that is a repeat is dropped; one without a result and one that is published are left alone
+    dropped, republished = [], []
+    mask = np.array([0, 1, 0, 0, 0, 0, 1], np.uint8)
+    repeats.apply_mask(mask, rep, {1: ("MU", "1", "aa"), 3: None, 5: ("MU", "2", "b")}, dropped.append, republished.append)
+    assert dropped == [1] and republished == [2]
+    # nothing differs and there is no host row: nothing is touched
+    repeats.apply_mask(rep, rep, {}, dropped.append, republished.append)
+    assert dropped == [1] and republished == [2]
+
+
 # ---- LineStream against a scripted engine -------------------------------------------------------------
 def line_key(ln: bytes):
     """A scripted line b'MU;K=<proto>:<payload>;...' -> its key, None without a K field."""

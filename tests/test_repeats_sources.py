@@ -196,6 +196,44 @@ def test_one_source_is_the_one_stream_entry(eng):
     assert 0 < sum(timed) < 400
 
 
+@pytest.mark.parametrize("n", [65, 257])     # one lane past a wave, one line past a tile
+def test_three_modes_through_repeat_pass(eng, n):
+    """repeats.RepeatPass drives each entry through alloc / enqueue.  Plain, timed with a window wider than
+    all the times, and by source with S = 1 and that window are one definition: the same masks -- restate's
+    -- over two chunks (the second starts from the carried state), and the same K in the three states."""
+    from pysignalduino_amd import runtime
+    from pysignalduino_amd.repeats import RepeatPass
+    rng = np.random.default_rng(n)
+    wide = 1 << 40
+    passes = [RepeatPass(eng), RepeatPass(eng, window_us=wide), RepeatPass(eng, window_us=wide, n_sources=1)]
+    carry, now = {}, 0
+    for chunk in range(2):
+        items = _random_items(rng, n)
+        items[-1] = items[-1] or A                     # the next chunk's first lines depend on this chunk's state
+        times = (now + np.cumsum(rng.integers(0, 1000, n))).astype(np.int64)
+        now = int(times[-1])
+        zeros = np.zeros(n, np.int32)
+        p = Planted(eng, items)
+        masks = []
+        for rp in passes:
+            b = rp.alloc(n, pinned=False)
+            b.mask.fill_(9)                            # every entry must be written
+            rp.enqueue(b, p.ins, n, times=times, sources=zeros)
+            masks.append(b.mask[:n].cpu().numpy().tolist())
+        exp = restate(keys_of(items), [0] * n, times.tolist(), None, carry)
+        assert masks[0] == exp and masks[1] == exp and masks[2] == exp, chunk
+        assert 0 < sum(exp) < n
+    plain, timed, slot0 = (rp.state.cpu().numpy() for rp in passes)
+    assert len(slot0) == len(timed)                    # S = 1: the one slot is a timed state
+    hdr = runtime.REPEAT_SLOT_HDR
+    K = plain[:16].view(np.uint32).tolist()
+    ln = K[3]
+    assert K[0] == 1 and (K[1], K[2], bytes(plain[16: 16 + ln])) == carry[0][0]
+    for st in (timed, slot0):
+        assert st[:16].view(np.uint32).tolist() == K and st[hdr: hdr + ln].tobytes() == plain[16: 16 + ln].tobytes()
+    assert timed[16:24].view(np.int64)[0] == slot0[16:24].view(np.int64)[0]
+
+
 def _id_patterns(n, S):
     rr = [i % S for i in range(n)]
     per = -(-n // S)
