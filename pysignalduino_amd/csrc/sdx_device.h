@@ -87,6 +87,11 @@ SDX_DEV uint64_t bcast_u64(uint64_t v, int src) {
 }
 SDX_DEV int ffs64(uint64_t x) { return __ffsll((unsigned long long)x) - 1; }  // -1 if zero
 SDX_DEV int popc64(uint64_t x) { return __popcll(x); }
+// orders the LDS accesses of one wave's lanes (no block barrier: the other waves are not waited for)
+SDX_DEV void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
 
 // bits p..p+63 of a position bitmap (bit i of word w = position 64w+i), reading words w and w+1
 SDX_DEV uint64_t bm_window(const uint64_t* bm, int w, int sh, int nw) {

@@ -41,20 +41,16 @@ SDX_DEV uint64_t peers8(uint32_t v, bool active) {
 // the clock-grouped processing order.)
 // ---------------------------------------------------------------------------------------------
 constexpr int SIG_PROTOS = 32;
-template <int KIND>
-SDX_DEV void sig_block(const void* __restrict__ bank, const sdx_pulse_batch& b, uint32_t* __restrict__ key,
-                       uint32_t* __restrict__ msg_out, sdx_msg_rec* __restrict__ mrec, const int blk) {
-  const BankView bv = bank_view(bank);
-  const int i = blk * 256 + threadIdx.x;
-  const int ntot = b.sel_dev ? b.n_sel : b.n;
-  const bool valid = i < ntot;
-  const int msg = valid ? (b.sel_dev ? b.sel_dev[i] : i) : 0;
-  int npat = valid ? b.npat_dev[msg] : 0;
-  npat = npat > SDX_MAXPAT ? SDX_MAXPAT : npat;
-  double val[SDX_MAXPAT];
-#pragma unroll
-  for (int k = 0; k < SDX_MAXPAT; ++k) val[k] = k < npat ? b.pat_val_dev[msg * SDX_MAXPAT + k] : 0.0;
-  int kq[SDX_MAXPAT];
+// The signature bits of one message from its pattern slots [0, NP), npat <= NP.  The kernel is bound by
+// the vector instructions of the slot loops below (32 protocols x up to 4 values x the slots), so a
+// wave none of whose messages has more than SIG_NARROW patterns (the receivers send at most 8) runs
+// them over SIG_NARROW slots instead of SDX_MAXPAT: an absent slot holds SDX_K_NONE, which passes no
+// interval test (k_in), so the slots left out change no bit.
+constexpr int SIG_NARROW = 8;
+template <int KIND, int NP>
+SDX_DEV uint32_t sig_bits(const BankView& bv, const sdx_pulse_batch& b, const double* val, const int npat,
+                          const bool valid, const int msg) {
+  int kq[NP];
   uint32_t sig = 0;
   // the candidate test of one search list: every unique value has a slot in [klo, khi]
   auto keys_ok = [&](const SpecV& sv) -> bool {
@@ -64,7 +60,7 @@ SDX_DEV void sig_block(const void* __restrict__ bank, const sdx_pulse_batch& b, 
       if (u < sv.nu) {
         bool any = false;
 #pragma unroll
-        for (int j = 0; j < SDX_MAXPAT; ++j) any |= k_in(kq[j], sv.klo[u], sv.khi[u]);
+        for (int j = 0; j < NP; ++j) any |= k_in(kq[j], sv.klo[u], sv.khi[u]);
         ok = ok && any;
       }
     }
@@ -73,25 +69,26 @@ SDX_DEV void sig_block(const void* __restrict__ bank, const sdx_pulse_batch& b, 
   if constexpr (KIND == SDX_KIND_MU) {
     // round(P / clockabs, 1) * 10 in fp32: the key only orders the work, so a value that lands on
     // the other side of an interval border than the exact fp64 test would costs nothing but grouping
-    float x10[SDX_MAXPAT];
+    float x10[NP];
 #pragma unroll
-    for (int k = 0; k < SDX_MAXPAT; ++k) x10[k] = (float)(val[k] * 10.0);
+    for (int k = 0; k < NP; ++k) x10[k] = (float)(val[k] * 10.0);
     const int nr = (int)bv.hdr->n_mu < SIG_PROTOS ? (int)bv.hdr->n_mu : SIG_PROTOS;
     double last = __builtin_nan("");
     for (int r = 0; r < nr; ++r) {
       const sdx_mu_filt* fr = uniform_ptr(bv.mufilt + r);
       const sdx_mu_proto* rec = uniform_ptr(bv.mu + r);
       const uint32_t ff = cld(&fr->flags);
-      bool ok = !(ff & 2u) && (ff & 4u);  // active, not never
+      const double pclk = cld(&fr->clock);  // with the flags: one wait for both scalar loads
+      bool ok = !(ff & 2u) && (ff & 4u);    // active, not never
       if (ok) {
-        const double pclk = cld(&fr->clock);
         if (pclk != last) {
           last = pclk;
           const float inv = 1.0f / (float)pclk;
 #pragma unroll
-          for (int k = 0; k < SDX_MAXPAT; ++k) {
+          for (int k = 0; k < NP; ++k) {
             const float q = x10[k] * inv;
-            kq[k] = (k < npat && fabsf(q) < 1.0e8f) ? (int)rintf(q) : SDX_K_NONE;
+            const bool in = (k < npat) & (fabsf(q) < 1.0e8f);
+            kq[k] = in ? (int)rintf(in ? q : 0.0f) : SDX_K_NONE;  // selects, not a branch per slot
           }
         }
         // the protocol's first search list: start if it has one, else one (the list whose test
@@ -113,9 +110,10 @@ SDX_DEV void sig_block(const void* __restrict__ bank, const sdx_pulse_batch& b, 
     const bool gate = valid && b.ms_ok_dev[msg] && cp >= 0 && cp < npat && clock != 0.0;
     const float inv = clock != 0.0 ? (float)(10.0 / clock) : 0.0f;  // fp32 is enough for a grouping key
 #pragma unroll
-    for (int k = 0; k < SDX_MAXPAT; ++k) {
+    for (int k = 0; k < NP; ++k) {
       const float q = (float)val[k] * inv;
-      kq[k] = (gate && k < npat && fabsf(q) < 1.0e8f) ? (int)rintf(q) : SDX_K_NONE;
+      const bool in = gate & (k < npat) & (fabsf(q) < 1.0e8f);
+      kq[k] = in ? (int)rintf(in ? q : 0.0f) : SDX_K_NONE;
     }
     const int nr = (int)bv.hdr->n_ms < SIG_PROTOS ? (int)bv.hdr->n_ms : SIG_PROTOS;
     for (int r = 0; r < nr; ++r) {
@@ -133,6 +131,24 @@ SDX_DEV void sig_block(const void* __restrict__ bank, const sdx_pulse_batch& b, 
       sig |= (uint32_t)ok << (31 - r);
     }
   }
+  return sig;
+}
+
+template <int KIND>
+SDX_DEV void sig_block(const void* __restrict__ bank, const sdx_pulse_batch& b, uint32_t* __restrict__ key,
+                       uint32_t* __restrict__ msg_out, sdx_msg_rec* __restrict__ mrec, const int blk) {
+  const BankView bv = bank_view(bank);
+  const int i = blk * 256 + threadIdx.x;
+  const int ntot = b.sel_dev ? b.n_sel : b.n;
+  const bool valid = i < ntot;
+  const int msg = valid ? (b.sel_dev ? b.sel_dev[i] : i) : 0;
+  int npat = valid ? b.npat_dev[msg] : 0;
+  npat = npat > SDX_MAXPAT ? SDX_MAXPAT : npat;
+  double val[SDX_MAXPAT];
+#pragma unroll
+  for (int k = 0; k < SDX_MAXPAT; ++k) val[k] = k < npat ? b.pat_val_dev[msg * SDX_MAXPAT + k] : 0.0;
+  const uint32_t sig = ballot(npat > SIG_NARROW) ? sig_bits<KIND, SDX_MAXPAT>(bv, b, val, npat, valid, msg)
+                                                 : sig_bits<KIND, SIG_NARROW>(bv, b, val, npat, valid, msg);
   if (valid && mrec) {  // the message's 128-byte record (sdx_msg_rec), eight 16-byte stores
     const int64_t off = b.offsets_dev[msg];
     const int32_t len = b.len_dev ? b.len_dev[msg] : (int32_t)(b.offsets_dev[msg + 1] - off);
@@ -193,20 +209,31 @@ __global__ __launch_bounds__(256) void k_sig2(const void* __restrict__ bank, Sig
 // elements; per pass the partitions' digit counts (k_rs_hist), their prefix over the partitions (a
 // wave per digit, k_rs_scan_rows) and the scatter (k_rs_scatter, which also scans the 256 digit
 // totals).  No inter-workgroup waiting: a decoupled look-back sort is latency-bound at these sizes.
+//
+// These workgroups run beside k_step, whose tiles fill the CUs: each one holds a tile's slot for as
+// long as it lives, so what counts is how long a workgroup lives, and beside busy waves that is
+// mostly its block barriers (each waits for the slowest of 8 waves to get issue slots).  Wave w of a
+// partition therefore owns the elements [RS_WAVE w, RS_WAVE (w + 1)) as RS_ROUNDS coalesced
+// sub-chunks of 64 and keeps them in registers, so that whatever orders the elements of one wave
+// needs wave_sync() only; the scatter has two block barriers and the counts two.
 // ---------------------------------------------------------------------------------------------
-constexpr int RS_T = 512, RS_ROUNDS = 4, RS_PART = RS_T * RS_ROUNDS;
+constexpr int RS_T = 512, RS_WAVES = RS_T / 64, RS_ROUNDS = 4, RS_WAVE = 64 * RS_ROUNDS, RS_PART = RS_T * RS_ROUNDS;
 constexpr int RS_PASSES = 4;  // bytes of the key sorted on, from the top
 
 // hist[digit * np + part] = elements of the partition with that digit in pass d
 SDX_DEV void rs_hist(const uint32_t* __restrict__ key, int n, int np, int d, uint32_t* __restrict__ hist, const int p,
                      uint32_t* c) {
   const int tid = threadIdx.x;
+  const int e0 = p * RS_PART + (tid >> 6) * RS_WAVE + (tid & 63);
+  uint32_t k[RS_ROUNDS];
+#pragma unroll
+  for (int s = 0; s < RS_ROUNDS; ++s) k[s] = e0 + 64 * s < n ? key[e0 + 64 * s] : 0u;  // all loads in flight at once
   if (tid < 256) c[tid] = 0;
   __syncthreads();
-  for (int r = 0; r < RS_ROUNDS; ++r) {
-    const int e = p * RS_PART + r * RS_T + tid;
-    const bool valid = e < n;
-    const uint32_t dig = valid ? (key[e] >> (8 * d)) & 255u : 0u;
+#pragma unroll
+  for (int s = 0; s < RS_ROUNDS; ++s) {
+    const bool valid = e0 + 64 * s < n;
+    const uint32_t dig = (k[s] >> (8 * d)) & 255u;
     const uint64_t peers = peers8(dig, valid);
     if (valid && lane_id() == ffs64(peers)) atomicAdd(&c[dig], (uint32_t)popc64(peers));
   }
@@ -224,16 +251,26 @@ SDX_DEV void rs_scan_rows(uint32_t* __restrict__ hist, int np, uint32_t* __restr
   const int row = blk * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   uint32_t* h = hist + (size_t)row * np;
   uint32_t run = 0;
-  for (int b0 = 0; b0 < np; b0 += 64) {
-    const int x = b0 + lane;
-    const uint32_t v = x < np ? h[x] : 0u;
-    uint32_t incl = v;
+  for (int b0 = 0; b0 < np; b0 += 256) {  // 4 partitions per lane: one shuffle scan per 256 partitions
+    const int x0 = b0 + 4 * lane;
+    uint32_t v[4], sum = 0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      v[c] = x0 + c < np ? h[x0 + c] : 0u;
+      sum += v[c];
+    }
+    uint32_t incl = sum;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
       const uint32_t y = __shfl_up(incl, o);
       if (lane >= o) incl += y;
     }
-    if (x < np) h[x] = run + incl - v;
+    uint32_t b = run + incl - sum;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      if (x0 + c < np) h[x0 + c] = b;
+      b += v[c];
+    }
     run += __shfl(incl, 63);
   }
   if (lane == 0) tot[row] = run;
@@ -246,52 +283,84 @@ __global__ __launch_bounds__(256) void k_rs_scan_rows(uint32_t* __restrict__ his
 // (digit base = prefix of the digit totals) + (row offset of the partition) + (rank inside it)
 SDX_DEV void rs_scatter(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin, int n, int np, int d,
                         const uint32_t* __restrict__ hist, const uint32_t* __restrict__ tot, uint32_t* __restrict__ kout,
-                        uint32_t* __restrict__ vout, const int p, uint32_t* run, uint32_t (*wc)[256]) {
-  const int tid = threadIdx.x, wave = tid >> 6;
-  const uint32_t t = tid < 256 ? tot[tid] : 0u;
-  if (tid < 256) run[tid] = t;
-  __syncthreads();
-  for (int o = 1; o < 256; o <<= 1) {  // inclusive scan of the digit totals
-    const uint32_t y = (tid < 256 && tid >= o) ? run[tid - o] : 0u;
-    __syncthreads();
-    if (tid < 256) run[tid] += y;
-    __syncthreads();
-  }
-  if (tid < 256) run[tid] = run[tid] - t + hist[(size_t)tid * np + p];
-  for (int r = 0; r < RS_ROUNDS; ++r) {
-    const int e = p * RS_PART + r * RS_T + tid;
-    const bool valid = e < n;
-    const uint32_t k = valid ? kin[e] : 0u;
-    const uint32_t v = valid ? vin[e] : 0u;
-    const uint32_t dig = (k >> (8 * d)) & 255u;
-    for (int x = tid; x < RS_T / 64 * 256; x += RS_T) (&wc[0][0])[x] = 0;
-    __syncthreads();
-    const uint64_t peers = peers8(dig, valid);
-    if (valid && lane_id() == ffs64(peers)) wc[wave][dig] = (uint32_t)popc64(peers);
-    __syncthreads();
-    if (valid) {
-      uint32_t pos = run[dig] + (uint32_t)lanes_below_mask(peers);
-      for (int w = 0; w < wave; ++w) pos += wc[w][dig];
-      kout[pos] = k;
-      vout[pos] = v;
-    }
-    __syncthreads();
-    if (tid < 256) {
-      uint32_t add = 0;
+                        uint32_t* __restrict__ vout, const int p, uint32_t* base, uint32_t (*wc)[256]) {
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int e0 = p * RS_PART + wave * RS_WAVE + lane;
+  uint32_t k[RS_ROUNDS], v[RS_ROUNDS];
 #pragma unroll
-      for (int w = 0; w < RS_T / 64; ++w) add += wc[w][tid];
-      run[tid] += add;
+  for (int s = 0; s < RS_ROUNDS; ++s) {
+    const bool valid = e0 + 64 * s < n;
+    k[s] = valid ? kin[e0 + 64 * s] : 0u;
+    v[s] = valid ? vin[e0 + 64 * s] : 0u;
+  }
+  // thread = digit (phase 2): the row offset of this partition
+  const uint32_t row = tid < 256 ? hist[(size_t)tid * np + p] : 0u;
+#pragma unroll
+  for (int x = 0; x < 4; ++x) wc[wave][64 * x + lane] = 0;
+  if (wave == RS_WAVES - 1) {  // base[digit] = exclusive prefix of the digit totals, 4 per lane
+    uint32_t t[4], sum = 0;
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      t[x] = tot[4 * lane + x];
+      sum += t[x];
     }
-    __syncthreads();
+    uint32_t incl = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t y = __shfl_up(incl, o);
+      if (lane >= o) incl += y;
+    }
+    uint32_t b = incl - sum;
+#pragma unroll
+    for (int x = 0; x < 4; ++x) {
+      base[4 * lane + x] = b;
+      b += t[x];
+    }
+  }
+  wave_sync();
+  // phase 1: wc[wave][digit] = this wave's elements with the digit; before[s] = those of them in the
+  // sub-chunks before s.  The leaders of one sub-chunk have distinct digits: no atomics
+  uint64_t peers[RS_ROUNDS];
+  uint32_t before[RS_ROUNDS];
+#pragma unroll
+  for (int s = 0; s < RS_ROUNDS; ++s) {
+    const bool valid = e0 + 64 * s < n;
+    const uint32_t dig = (k[s] >> (8 * d)) & 255u;
+    peers[s] = peers8(dig, valid);
+    before[s] = wc[wave][dig];
+    wave_sync();
+    if (valid && lane == ffs64(peers[s])) wc[wave][dig] = before[s] + (uint32_t)popc64(peers[s]);
+    wave_sync();
+  }
+  __syncthreads();
+  // phase 2: the 8 waves' counts of a digit -> where each wave's elements with that digit start
+  if (tid < 256) {
+    uint32_t run = base[tid] + row;
+#pragma unroll
+    for (int w = 0; w < RS_WAVES; ++w) {
+      const uint32_t c = wc[w][tid];
+      wc[w][tid] = run;
+      run += c;
+    }
+  }
+  __syncthreads();
+  // phase 3: (wave, sub-chunk, lane) is the index order, so the sort is stable
+#pragma unroll
+  for (int s = 0; s < RS_ROUNDS; ++s) {
+    if (e0 + 64 * s < n) {
+      const uint32_t pos = wc[wave][(k[s] >> (8 * d)) & 255u] + before[s] + (uint32_t)lanes_below_mask(peers[s]);
+      kout[pos] = k[s];
+      vout[pos] = v[s];
+    }
   }
 }
 __global__ __launch_bounds__(RS_T) void k_rs_scatter(const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin,
                                                      int n, int np, int d, const uint32_t* __restrict__ hist,
                                                      const uint32_t* __restrict__ tot, uint32_t* __restrict__ kout,
                                                      uint32_t* __restrict__ vout) {
-  __shared__ uint32_t run[256];
-  __shared__ uint32_t wc[RS_T / 64][256];
-  rs_scatter(kin, vin, n, np, d, hist, tot, kout, vout, (int)blockIdx.x, run, wc);
+  __shared__ uint32_t base[256];
+  __shared__ uint32_t wc[RS_WAVES][256];
+  rs_scatter(kin, vin, n, np, d, hist, tot, kout, vout, (int)blockIdx.x, base, wc);
 }
 
 // one radix pass of two sorts in each launch (sdx_group_step): partitions [0, a.np) sort a's keys,
@@ -317,12 +386,12 @@ __global__ __launch_bounds__(256) void k_rs_scan_rows2(RsPass a, RsPass b) {
   rs_scan_rows(x.hist, x.np, x.tot, (int)blockIdx.x - (second ? 256 / 4 : 0));
 }
 __global__ __launch_bounds__(RS_T) void k_rs_scatter2(RsPass a, RsPass b, int d) {
-  __shared__ uint32_t run[256];
-  __shared__ uint32_t wc[RS_T / 64][256];
+  __shared__ uint32_t base[256];
+  __shared__ uint32_t wc[RS_WAVES][256];
   const bool second = (int)blockIdx.x >= a.np;
   const RsPass& x = second ? b : a;
   rs_scatter(x.kin, x.vin, x.n, x.np, d, x.hist, x.tot, x.kout, x.vout,
-             second ? (int)blockIdx.x - a.np : (int)blockIdx.x, run, wc);
+             second ? (int)blockIdx.x - a.np : (int)blockIdx.x, base, wc);
 }
 
 constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }

@@ -202,11 +202,6 @@ struct TileLds {
 #endif
 };
 
-SDX_DEV void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // OR over each aligned group of G (8 or 16) lanes, in every lane of the group, by DPP within a row
 // of 16: the quad's other three lanes (quad_perm [1,0,3,2], [2,3,0,1]), the half row's other quad
 // (row_half_mirror), the row's other half (row_mirror).  All lanes of the wave must be active.

@@ -1,5 +1,5 @@
 """The per-step grouping alone (nothing beside it): sdx_group_pulses of the bench step's MU and MS
-batches (333k messages each), timed with HIP events; run under rocprofv3 --kernel-trace --stats for
+batches (333k messages each) and the sdx_group_step of both, timed with HIP events; run under rocprofv3 --kernel-trace --stats for
 its kernels' uncontended durations.  usage: python tools/time_group.py [reps]"""
 import os
 import sys
@@ -38,6 +38,19 @@ def main():
         ts["MS"].append(ev[1].elapsed_time(ev[2]))
         ts["both"].append(ev[0].elapsed_time(ev[2]))
     print("grouping alone (ms, median): " + ", ".join(f"{k} {np.median(v):.4f}" for k, v in ts.items()), flush=True)
+    # the step's form: both sorts in the same launches (sdx_group_step)
+    for _ in range(3):
+        eng.group_step(bds["MU"], bds["MS"], gb["MU"], gb["MS"])
+    torch.cuda.synchronize()
+    st = []
+    for _ in range(reps):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        eng.group_step(bds["MU"], bds["MS"], gb["MU"], gb["MS"])
+        ev[1].record()
+        torch.cuda.synchronize()
+        st.append(ev[0].elapsed_time(ev[1]))
+    print(f"group_step alone (ms): median {np.median(st):.4f}, min {min(st):.4f}", flush=True)
 
 
 if __name__ == "__main__":
