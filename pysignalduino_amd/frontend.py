@@ -629,6 +629,36 @@ class SignalParser:
                     eng.launch_pulses(kind, bd, out, sel=sel, long_variant=long_v)
             return out
 
+        def rerun_tile_overflows(kind, out, rec_cap, heap_cap):
+            """An MU/MS launch whose cursor[2] is 2: tiles overflowed their on-chip staging and found no
+            spill region left (ST_OVF_TILE), which larger outputs cannot cure.  Those messages re-run on
+            the long variant into an overlay, as Engine.run does; returns the launch and the overlay as
+            one output (merge_overlay), which the repeat pass and the serialiser read like any other."""
+            st = out["desc"][: 8 * n].view(-1, 8)[:, 6].cpu().numpy()
+            redo = np.nonzero(st == runtime.ST_OVF_TILE)[0].astype(np.int32)
+            for _attempt in range(4):
+                ov = eng.rerun_overlay(kind, pb, redo, rec_cap, heap_cap)
+                c = ov["cursor"].cpu().numpy()
+                if c[2] & 2:
+                    raise RuntimeError("result staging overflow persists (pathological message)")
+                if not c[2]:
+                    return eng.merge_overlay(out, ov, redo)
+                rec_cap, heap_cap = 4 * rec_cap, 4 * heap_cap
+            raise RuntimeError("result capacity overflow persists")
+
+        def serialize(kind, out, json_cap, skip=None):
+            """The launch's texts into a fresh buffer, grown until they fit: (buffers, bytes used)."""
+            for _attempt in range(4):
+                jo = eng.alloc_json(n, json_cap)
+                eng.launch_json(kind, out, lo, n, jo, first_only=True, skip=skip)
+                c2 = jo["cursor"].cpu().numpy()
+                if not c2[1]:
+                    return jo, c2[0]
+                json_cap *= 4
+            raise RuntimeError("JSON capacity overflow persists")
+
+        pulses = (runtime.KIND_MU, runtime.KIND_MS)
+
         def take_texts(jo, used):
             lens = jo["len"][:n].cpu().numpy()
             offs = jo["off"][:n].cpu().numpy()
@@ -653,9 +683,12 @@ class SignalParser:
                         st = out["desc"][: 8 * n].view(-1, 8)[:, 6][sel.long()].cpu().numpy()
                         host_rows.extend(int(i) for i in sel.cpu().numpy()[st == runtime.ST_OVF_TILE])
                         break
+                    if kind in pulses and c1[2] == 2:   # only tile overflows are left: not a capacity matter
+                        out = rerun_tile_overflows(kind, out, rec_cap, heap_cap)
+                        break
                     if not c1[2]:
                         break
-                    rec_cap, heap_cap = 4 * rec_cap, 4 * heap_cap
+                    rec_cap, heap_cap = 4 * rec_cap, 4 * heap_cap   # bit 0: the outputs overflowed
                 else:
                     raise RuntimeError("result capacity overflow persists")
                 kept.append((kind, out, json_cap))
@@ -664,16 +697,7 @@ class SignalParser:
                 rpass.enqueue(rbufs, [eng.json_in(kind, out, lo, n) for kind, out, _ in kept], n, times=times,
                               sources=sources)
                 for kind, out, json_cap in kept:
-                    for _attempt in range(4):
-                        jo = eng.alloc_json(n, json_cap)
-                        eng.launch_json(kind, out, lo, n, jo, first_only=True, skip=rbufs.mask)
-                        c2 = jo["cursor"].cpu().numpy()
-                        if not c2[1]:
-                            break
-                        json_cap *= 4
-                    else:
-                        raise RuntimeError("JSON capacity overflow persists")
-                    take_texts(jo, c2[0])
+                    take_texts(*serialize(kind, out, json_cap, skip=rbufs.mask))
                 rep = rbufs.mask[:n].cpu().numpy()
             jobs = []
         for kind, rec_cap, heap_cap, json_cap, launches in jobs:
@@ -688,6 +712,12 @@ class SignalParser:
                     sel = launches[0][1]
                     st = out["desc"][: 8 * n].view(-1, 8)[:, 6][sel.long()].cpu().numpy()
                     host_rows.extend(int(i) for i in sel.cpu().numpy()[st == runtime.ST_OVF_TILE])
+                    break
+                if kind in pulses and c1[2] == 2:
+                    # only tile overflows are left: not a capacity matter.  The texts again, from the launch
+                    # merged with the re-run of those messages
+                    jo, used = serialize(kind, rerun_tile_overflows(kind, out, rec_cap, heap_cap), json_cap)
+                    c2 = (used, 0)
                     break
                 if not c1[2] and not c2[1]:
                     break

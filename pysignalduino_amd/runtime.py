@@ -604,12 +604,15 @@ class Engine:
         out["lengths"] = np.diff(arrs["offsets"])
         return out
 
-    def run_general(self, kind: int, gd, work_stride: int = 0):
+    def run_general(self, kind: int, gd, work_stride: int = 0, rec_cap: Optional[int] = None,
+                    heap_cap: Optional[int] = None):
         """MU/MS messages on the general path; returns host (desc, rec, heap) like run().
-        ``work_stride`` > 0: per-message scratch of that many bytes (gd in slot layout, "len" set)."""
+        ``work_stride`` > 0: per-message scratch of that many bytes (gd in slot layout, "len" set).
+        ``rec_cap`` / ``heap_cap``: the first attempt's output capacities (default: sized by the batch);
+        an overflow re-runs the batch with both grown."""
         n = gd["n"]
-        rec_cap = 16 * n + 1024
-        heap_cap = int(2 * gd["total"] + 256 * n + 65536)
+        rec_cap = 16 * n + 1024 if rec_cap is None else int(rec_cap)
+        heap_cap = int(2 * gd["total"] + 256 * n + 65536) if heap_cap is None else int(heap_cap)
         lens = gd["lens_host"] if "lens_host" in gd else np.asarray(gd["lengths"])
         max_len = int(lens.max(initial=0))
         wb = int(self.lib.sdx_general_work_bytes(self.handle, kind, int(gd["total"]), n, max_len, int(work_stride)))
@@ -963,6 +966,33 @@ class Engine:
             self.launch_pulses(kind, bd, out2, sel=sel, long_variant=True)
         out2["_sel"] = sel          # alive until the launches have run
         return out2
+
+    def merge_overlay(self, out, ov, redo: np.ndarray):
+        """A launch's outputs and the overlay that re-ran its messages ``redo`` (rerun_overlay) as ONE
+        output dict on the device, for what reads a launch through its descriptors (launch_json,
+        mark_repeats): the overlay's records and payloads appended after the launch's, re-based as run()
+        re-bases them on the host, and the descriptors of ``redo`` taken from the overlay.  Index
+        plumbing of a rare path (one host read of the two cursors); the cursor's overflow word is the
+        overlay's."""
+        t = self.torch
+        c0 = out["cursor"].cpu().numpy().astype(np.uint32)
+        c1 = ov["cursor"].cpu().numpy().astype(np.uint32)
+        r0, h0 = min(int(c0[0]), out["rec_cap"]), min(int(c0[1]), out["heap_cap"])
+        r1, h1 = min(int(c1[0]), ov["rec_cap"]), min(int(c1[1]), ov["heap_cap"])
+        rs = RES_DT.itemsize
+        rec1 = ov["rec"][: r1 * rs].view(t.int32).view(-1, rs // 4).clone()
+        rec1[:, 0] += h0                                   # sdx_result.payload_off
+        idx = t.from_numpy(np.asarray(redo, np.int64)).to(self.dev)
+        desc = out["desc"].clone()
+        d0 = desc[: out["n"] * DESC_DT.itemsize].view(t.int32).view(-1, 2)
+        d1 = ov["desc"][: out["n"] * DESC_DT.itemsize].view(t.int32).view(-1, 2)[idx].clone()
+        d1[:, 0] += r0                                     # sdx_desc.rec_begin
+        d0[idx] = d1
+        # (one spare record / byte behind the declared capacities: never an empty buffer)
+        return {"desc": desc, "rec": t.cat([out["rec"][: r0 * rs], rec1.view(-1).view(t.uint8), out["rec"][:rs]]),
+                "heap": t.cat([out["heap"][:h0], ov["heap"][:h1], out["heap"][:1]]),
+                "cursor": t.tensor([r0 + r1, h0 + h1, int(c1[2]), int(c0[3])], dtype=t.int32, device=self.dev),
+                "work": None, "wire": None, "xrec": None, "rec_cap": r0 + r1, "heap_cap": h0 + h1, "n": out["n"]}
 
     def fetch(self, out):
         self.torch.cuda.current_stream(self.dev).synchronize()
