@@ -539,6 +539,37 @@ int sdx_mark_repeats_by_source(const sdx_bank* bank, const sdx_json_in* kinds, i
                                int64_t window_us, uint8_t* repeat_dev, void* scratch_dev, void* state_dev,
                                void* hip_stream);
 
+/* ---- payload routes --------------------------------------------------------------
+ * FHEM's step behind the equal-message drop: the dispatched string is matched against an ordered client
+ * list and goes to the first client whose regex matches.  A ROUTE TABLE is an ordered list of up to 64
+ * (name, pattern) pairs, compiled on the host (pysignalduino_amd/routes.py) into one search DFA per route
+ * over a shared byte-class alphabet; the blob's layout and its validator: csrc/sdx_route_layout.h.
+ * For a result-bearing line (as above: SDX_ST_OK with n_rec > 0 in its kind's launch) with the payload of
+ * its first record: mask bit r is set iff re.search(pattern_r, payload) finds a match, route = the lowest
+ * set bit, -1 = none.  A line without a result has mask 0 and route -1.  An empty payload is decided by
+ * the start state's flags.
+ * sdx_route_table_create validates the WHOLE blob on the host (magic, version, every offset and size
+ * inside nbytes, every cls_of entry below the class count, every transition and start state below its
+ * DFA's state count) before anything is uploaded: a bad blob gives SDX_EINVAL and no device call.  The
+ * kernel therefore tests no table contents.  sdx_route_table_lds_routes: how many of the table's routes
+ * the kernel serves from LDS (the first ones, as far as SDX_ROUTE_LDS_BYTES reach); the others walk their
+ * tables in global memory.
+ * sdx_route_lines, one kernel on the caller's stream (lane = line): kinds[0..k) as sdx_mark_repeats takes
+ * them.  route_dev [n] int16; mask_dev [n] uint64 or NULL (then a lane stops at its first match; route_dev
+ * is the same); skip_dev [n] uint8 or NULL: skip_dev[g] = (repeat_dev && repeat_dev[g]) || (drop_unrouted
+ * && result-bearing(g) && route(g) < 0), what sdx_serialize_json_skip takes.  repeat_dev: sdx_mark_repeats'
+ * mask or NULL; routing never changes it.  Every entry of the given outputs in [0, n) is written.  No
+ * allocation, no synchronisation, no global atomics, nothing read past a payload's end.  SDX_EINVAL
+ * (nothing launched): a null table or route_dev, a misaligned route_dev (2 bytes) / mask_dev (8), bad
+ * kinds, n < 0. */
+typedef struct sdx_route_table sdx_route_table;
+int sdx_route_table_create(const void* blob, size_t nbytes, int device, sdx_route_table** out);
+int sdx_route_table_destroy(sdx_route_table* table);
+int sdx_route_table_lds_routes(const sdx_route_table* table);
+int sdx_route_lines(const sdx_bank* bank, const sdx_route_table* table, const sdx_json_in* kinds, int k, int32_t n,
+                    const uint8_t* repeat_dev, int drop_unrouted, int16_t* route_dev, uint64_t* mask_dev,
+                    uint8_t* skip_dev, void* hip_stream);
+
 /* ---- unit-level entry ------------------------------------------------------------------------
  * The reference's helper methods that its own unit tests call on SDProtocols, evaluated on n
  * independent inputs in one launch (lane = item), with the device code the demodulation kernels

@@ -42,6 +42,13 @@ micro-batches.  ``repeat_window=SECONDS`` (with ``collapse_repeats``) also ends 
 published telegram is more than the window old, as FHEM dispatches (repeats.py): every line is stamped
 with ``time.monotonic_ns() // 1000`` when it is taken from ``_raw_message_queue`` (``clock``: another
 source of microseconds, for tests), and the stamps travel with the lines to the parser.
+
+``routes`` (a routes.RouteTable or a list of (name, regex) pairs; with ``publish="json"``) matches every
+decoded telegram's payload against an ordered client list on the device.
+``route_topics=True`` publishes a routed text to ``<base_topic>/state/messages/<name>`` and an unrouted one
+to ``<base_topic>/state/messages``; ``drop_unrouted=True`` publishes nothing for a telegram no route
+matches (its text is never built) -- its line keeps its ``_handle_as_command_response`` turn, and it
+starts and breaks runs of repeats as before.  The defaults publish exactly as without routes.
 """
 from __future__ import annotations
 
@@ -56,9 +63,18 @@ class BatchingParserTask:
     def __init__(self, controller: Any, max_batch: int = 4096, max_delay: float = 0.005, publish: str = "objects",
                  logger: Optional[logging.Logger] = None, stream: bool = True, lag: int = 3,
                  collapse_repeats: bool = False, repeat_window: Optional[float] = None,
-                 clock: Optional[Callable[[], int]] = None):
+                 clock: Optional[Callable[[], int]] = None, routes=None, drop_unrouted: bool = False,
+                 route_topics: bool = False):
         if publish not in ("objects", "json"):
             raise ValueError("publish must be 'objects' or 'json'")
+        # payload routes: the texts' routes come from the device, so they need publish='json'
+        from .routes import as_table
+        self.routes = as_table(routes)
+        self.drop_unrouted, self.route_topics = bool(drop_unrouted), bool(route_topics)
+        if (self.drop_unrouted or self.route_topics) and self.routes is None:
+            raise ValueError("drop_unrouted / route_topics need routes")
+        if self.routes is not None and publish != "json":
+            raise ValueError("routes need publish='json'")
         if publish == "json" and getattr(controller, "message_callback", None):
             raise ValueError("publish='json' produces texts only; message_callback needs publish='objects'")
         if max_batch < 1:
@@ -153,14 +169,31 @@ class BatchingParserTask:
             return None
         return [t for ln, t in zip(batch, self._stamps) if ln]
 
-    async def _publish_json(self, text: str) -> None:
+    def _topic(self, base: str, route: int) -> str:
+        """<base>/state/messages, with route_topics <base>/state/messages/<name> for a routed text."""
+        if self.route_topics and route >= 0:
+            return f"{base}/state/messages/{self.routes.names[route]}"
+        return f"{base}/state/messages"
+
+    def _route_kw(self) -> dict:
+        return {} if self.routes is None else {"routes": self.routes, "drop_unrouted": self.drop_unrouted}
+
+    @staticmethod
+    def _routed_items(r) -> List[Any]:
+        """A routed chunk's items: (line, (route, text)), a ContractError as it is."""
+        return [(i, (route, x) if isinstance(x, str) else x) for i, route, x in r.items_routed()]
+
+    async def _publish_json(self, text: Any) -> None:
+        route = -1
+        if isinstance(text, tuple):   # routes: (route, text)
+            route, text = text
         pub = self.c.mqtt_publisher
         client = getattr(pub, "client", None)
         if not client:
             self.logger.warning("Attempted to publish without an active MQTT client.")
             return
         try:
-            await client.publish(f"{pub.base_topic}/state/messages", text)
+            await client.publish(self._topic(pub.base_topic, route), text)
         except Exception:  # noqa: BLE001  (mqtt.py:271-272)
             self.logger.error("Failed to publish message", exc_info=True)
 
@@ -213,7 +246,10 @@ class BatchingParserTask:
                     log.warning("Attempted to publish without an active MQTT client.")
                 else:
                     try:
-                        await client.publish(topic, res)
+                        if isinstance(res, tuple):   # routes: (route, text)
+                            await client.publish(self._topic(pub.base_topic, res[0]), res[1])
+                        else:
+                            await client.publish(topic, res)
                     except Exception:  # noqa: BLE001  (mqtt.py:271-272)
                         log.error("Failed to publish message", exc_info=True)
                     quiet = not (pend or dbg(D))
@@ -239,7 +275,7 @@ class BatchingParserTask:
             kw = {"collapse_repeats": True} if self.collapse else {}
             if self.window_us is not None:
                 kw["repeat_window"] = self.window_us / 1e6
-            self._stream = c.parser.stream(chunk_lines=self.max_batch, output="json", lag=self.lag, **kw)
+            self._stream = c.parser.stream(chunk_lines=self.max_batch, output="json", lag=self.lag, **kw, **self._route_kw())
         ls = self._stream
         # chunk id -> its lines: results are matched to their lines by id, never by position, so a
         # publication that fails part-way through a chunk cannot shift later chunks onto the wrong lines
@@ -253,8 +289,8 @@ class BatchingParserTask:
             while ready:
                 r = ready.popleft()
                 blines = pending.pop(r.id)
-                items = r.items() if hasattr(r, "items") else [(i, t) for i, t in enumerate(r.texts())
-                                                              if t is not None]
+                items = (self._routed_items(r) if self.routes is not None else
+                         r.items() if hasattr(r, "items") else [(i, t) for i, t in enumerate(r.texts()) if t is not None])
                 self.lines += len(blines)
                 await self._publish_items(blines, items)
 
@@ -296,9 +332,16 @@ class BatchingParserTask:
         if self.publish == "json":
             if self._stream is None:
                 kw = {} if times is None else {"repeat_window": self.window_us / 1e6}
-                self._stream = p.stream(chunk_lines=self.max_batch, output="json", lag=1, collapse_repeats=True, **kw)
+                self._stream = p.stream(chunk_lines=self.max_batch, output="json", lag=1, collapse_repeats=True, **kw,
+                                        **self._route_kw())
             self._stream.submit(lines, **({} if times is None else {"times": times}))
-            return self._stream.drain()[0].texts()
+            r = self._stream.drain()[0]
+            if self.routes is None:
+                return r.texts()
+            out: List[Any] = [None] * len(lines)
+            for i, x in self._routed_items(r):
+                out[i] = x
+            return out
         if times is not None:
             from .repeats import collapse_objects
             results = p.parse_lines(lines)
@@ -317,6 +360,9 @@ class BatchingParserTask:
             self._last_key = k
         return results
 
+    def _parse_routed(self, lines: List[Any]) -> List[Any]:
+        return self.c.parser.parse_lines_routed(lines, self.routes, drop_unrouted=self.drop_unrouted)
+
     async def run(self) -> None:
         c = self.c
         if self.use_stream:
@@ -327,6 +373,7 @@ class BatchingParserTask:
                 lines = list(filter(None, batch))
                 if lines:
                     parse = (self._parse_collapsed if self.collapse else
+                             self._parse_routed if self.routes is not None else
                              c.parser.parse_lines_json if self.publish == "json" else c.parser.parse_lines)
                     times = self._times_of(batch)
                     results = await asyncio.to_thread(parse, lines, *([] if times is None else [times]))

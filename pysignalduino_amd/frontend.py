@@ -29,7 +29,7 @@ import logging
 import re
 from dataclasses import dataclass, field
 from datetime import datetime
-from typing import Any, List, Optional, Sequence, Union
+from typing import Any, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -547,16 +547,22 @@ class SignalParser:
     # ------------------------------------------------------------------------------------------
     def stream(self, chunk_lines: int = 250_000, chunk_bytes: Optional[int] = None, output: str = "json",
                lag: int = 3, collapse_repeats: bool = False, repeat_window: Optional[float] = None,
-               repeat_sources: Optional[int] = None):
+               repeat_sources: Optional[int] = None, routes=None, drop_unrouted: bool = False):
         """A pipelined LineStream over this parser (pysignalduino_amd/stream.py): chunks of raw lines
         in, the controller's JSON texts (or the wire form) out, the PCIe copies, parse, demodulation
         and serialisation of successive chunks overlapping; the same per-line results as
         parse_lines_json / parse_lines.  ``repeat_sources``: the stream merges that many receivers, every
-        submit names its lines' source ids and repeat suppression runs per source (stream.py)."""
+        submit names its lines' source ids and repeat suppression runs per source (stream.py).  ``routes``
+        (a routes.RouteTable or a list of (name, pattern) pairs) / ``drop_unrouted``: payload routes, as
+        parse_lines_routed: ChunkResult.route and items_routed(); None leaves the stream as it is."""
         from .stream import LineStream
         kw = {} if repeat_window is None else {"repeat_window": repeat_window}
         if repeat_sources is not None:
             kw["repeat_sources"] = repeat_sources
+        if routes is not None:
+            kw.update(routes=routes, drop_unrouted=drop_unrouted)
+        elif drop_unrouted:
+            raise ValueError("drop_unrouted needs routes")
         return LineStream(self, chunk_lines=chunk_lines, chunk_bytes=chunk_bytes, output=output, lag=lag,
                           collapse_repeats=collapse_repeats, **kw)
 
@@ -584,9 +590,36 @@ class SignalParser:
         return self._texts(lines, LineBatch(self.protocols._ensure(), data, offsets), bad, len(data), collapse_repeats,
                            times, w, sources)
 
+    def parse_lines_routed(self, lines: Sequence[Union[str, bytes]], routes, drop_unrouted: bool = False,
+                           collapse_repeats: bool = False, times=None, repeat_window: Optional[float] = None,
+                           sources=None) -> List[Union[None, Tuple[int, str], Exception]]:
+        """parse_lines_json with payload routes: per line None, or (route_index, text) -- the
+        text parse_lines_json gives, and the index of the first route of ``routes`` (a routes.RouteTable or
+        a list of (name, pattern) pairs) whose pattern matches the payload of ``decoded[0]`` by ``re.search``,
+        -1 when none does.  Matched on the device (sdx_route_lines) behind the repeat pass, if any, and in
+        front of the serialiser; host-resolved lines are matched with RouteTable.match.  ``drop_unrouted``:
+        an unrouted line gives None (published = result-bearing, no repeat, routed); routing never changes
+        which lines are repeats.  The other arguments, and ContractError slots, as parse_lines_json.  The
+        lines' routes are left in ``last_routes`` (int16, -1 also for lines without a result)."""
+        from .routes import as_table
+        table = as_table(routes)
+        if table is None:
+            raise ValueError("parse_lines_routed needs a route table")
+        sources = self._source_args(collapse_repeats, sources, len(lines))
+        times, w = self._window_args(collapse_repeats, times, repeat_window, len(lines), sources)
+        if len(lines) == 0:
+            if collapse_repeats:
+                self.last_repeat_mask = np.zeros(0, np.uint8)
+            self.last_routes = np.zeros(0, np.int16)
+            return []
+        data, offsets, bad = pack_lines(lines)
+        return self._texts(lines, LineBatch(self.protocols._ensure(), data, offsets), bad, len(data), collapse_repeats,
+                           times, w, sources, routes=table, drop_unrouted=drop_unrouted)
+
     def _texts(self, lines, lb: LineBatch, bad: dict, nbytes: int, collapse: bool = False, times=None,
-               window_us: Optional[int] = None, sources=None):
-        """parse_lines_json from the uploaded batch on (``lines`` and ``nbytes`` as in _objects)."""
+               window_us: Optional[int] = None, sources=None, routes=None, drop_unrouted: bool = False):
+        """parse_lines_json from the uploaded batch on (``lines`` and ``nbytes`` as in _objects).  ``routes``
+        (a routes.RouteTable; parse_lines_routed): every text becomes (route, text), see there."""
         n = len(lines)
         eng = self.protocols._ensure()
         bk = self.protocols._bank
@@ -667,10 +700,12 @@ class SignalParser:
                 texts[int(i)] = blob[int(offs[i]): int(offs[i]) + int(lens[i])].decode("ascii")
 
         rep = np.zeros(n, np.uint8)   # the device's repeat mask (collapse)
+        route = np.full(n, -1, np.int16)   # the lines' routes (routes)
         if collapse:
             from .repeats import RepeatPass, apply_mask, count_sources, objects_key, text_key
             rpass = RepeatPass(eng, window_us, None if sources is None else count_sources(sources))
             rbufs = None
+        if collapse or routes is not None:
             # every kind's launch first (their outputs stay on the device), then ONE sdx_mark_repeats over
             # them, then the serialiser with the mask: a repeat is never turned into text
             kept = []
@@ -693,12 +728,25 @@ class SignalParser:
                     raise RuntimeError("result capacity overflow persists")
                 kept.append((kind, out, json_cap))
             if kept:   # a fresh stream of lines per call; nothing is read back but the mask (and the sources' table)
-                rbufs = rpass.alloc(n, pinned=False)
-                rpass.enqueue(rbufs, [eng.json_in(kind, out, lo, n) for kind, out, _ in kept], n, times=times,
-                              sources=sources)
+                ins = [eng.json_in(kind, out, lo, n) for kind, out, _ in kept]
+                skip = None
+                if collapse:
+                    rbufs = rpass.alloc(n, pinned=False)
+                    rpass.enqueue(rbufs, ins, n, times=times, sources=sources)
+                    skip = rbufs.mask
+                if routes is not None:
+                    # behind the repeat pass, in front of the serialiser.  With collapse the host needs the key
+                    # of every line that is no repeat (RepeatTracker), so unrouted texts still come back and are
+                    # dropped below; without it the device leaves them out
+                    rb = eng.alloc_routes(n, mask=False, skip=not collapse and drop_unrouted)
+                    eng.route_lines(eng.route_table(routes), ins, n, rb["route"], None, rb["skip"], drop_unrouted=drop_unrouted)
+                    skip = rb["skip"] if rb["skip"] is not None else skip
                 for kind, out, json_cap in kept:
-                    take_texts(*serialize(kind, out, json_cap, skip=rbufs.mask))
-                rep = rbufs.mask[:n].cpu().numpy()
+                    take_texts(*serialize(kind, out, json_cap, skip=skip))
+                if collapse:
+                    rep = rbufs.mask[:n].cpu().numpy()
+                if routes is not None:
+                    route = rb["route"][:n].cpu().numpy()
             jobs = []
         for kind, rec_cap, heap_cap, json_cap, launches in jobs:
             for _attempt in range(4):
@@ -747,6 +795,8 @@ class SignalParser:
                 elif g:
                     texts[i] = json.dumps({"protocol_id": g[0].protocol_id, "payload": g[0].payload,
                                            "metadata": g[0].metadata}, indent=4)
+                    if routes is not None:   # a host-resolved line: the same tables, walked on the host
+                        route[i] = routes.match(g[0].payload)[0]
         for i in range(n):
             if i in bad:
                 texts[i] = bad[i]
@@ -771,6 +821,11 @@ class SignalParser:
                 texts[i] = fetched[i] if i in fetched else self.parse_lines_json([lines[i]])[0]
             apply_mask(mask, rep, host_keys, drop, republish)
             self.last_repeat_mask = mask
+        if routes is not None:
+            self.last_routes = route
+            for i, x in enumerate(texts):
+                if isinstance(x, str):
+                    texts[i] = None if drop_unrouted and route[i] < 0 else (int(route[i]), x)
         return texts
 
     # -- byte-stream input ---------------------------------------------------------------------------

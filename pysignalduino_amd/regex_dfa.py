@@ -275,8 +275,9 @@ class CompiledDfa:
         return bool(self.flags[st] & ACC_END)
 
 
-def compile_pattern(pattern: str):
-    """Return (charsets used, per-state transition function on bytes, flags, start)."""
+def compile_pattern(pattern: str, max_states: Optional[int] = None):
+    """Return (charsets used, per-state transition function on bytes, flags, start).
+    ``max_states``: ValueError naming the pattern as soon as the subset construction exceeds it."""
     ast = _Parser(pattern).parse()
     nfa = _Nfa()
     s0 = nfa.new()
@@ -301,6 +302,8 @@ def compile_pattern(pattern: str):
     flags: List[int] = []
     k = 0
     while k < len(order):
+        if max_states is not None and len(order) > max_states:
+            raise ValueError(f"pattern {pattern!r}: its DFA has more than {max_states} states")
         key = order[k]
         if key == ACCEPT:
             flags.append(ACC_NOW | ACC_END)
@@ -339,12 +342,12 @@ def compile_pattern(pattern: str):
     return charsets, full, flags, 0, acc
 
 
-def compile_bank_dfas(patterns: Sequence[str]):
-    """Compile all patterns over one shared byte-class alphabet.
+def compile_bank_dfas(patterns: Sequence[str], max_states: Optional[int] = None):
+    """Compile all patterns over one shared byte-class alphabet (``max_states``: as compile_pattern).
 
     Returns (cls_of[256] -> class id, n_class, list of (nstates, start, trans[nstates][n_class], flags)).
     """
-    compiled = [compile_pattern(p) for p in patterns]
+    compiled = [compile_pattern(p, max_states) for p in patterns]
     # byte equivalence: two bytes are equivalent iff every DFA row treats them the same
     sig: Dict[Tuple, int] = {}
     cls_of = [0] * 256

@@ -50,7 +50,8 @@ EXPORTED = ["sdx_abi_version", "sdx_last_error", "sdx_source_hash", "sdx_layout_
             "sdx_host_count_byte", "sdx_serialize_json_skip", "sdx_mark_repeats", "sdx_repeat_state_bytes",
             "sdx_repeat_scratch_bytes", "sdx_repeat_tile", "sdx_mark_repeats_timed", "sdx_repeat_timed_state_bytes",
             "sdx_repeat_timed_scratch_bytes", "sdx_mark_repeats_by_source", "sdx_repeat_sources_state_bytes",
-            "sdx_repeat_sources_scratch_bytes"]
+            "sdx_repeat_sources_scratch_bytes", "sdx_route_table_create", "sdx_route_table_destroy",
+            "sdx_route_table_lds_routes", "sdx_route_lines"]
 REPEAT_SOURCES_MAX = 4096   # SDX_REPEAT_SOURCES_MAX
 # sdx_repeat_source_entry (csrc/sdx_repeat_layout.h): a source's slot header after a chunk + its last result-bearing line
 REPEAT_SOURCE_ENTRY = np.dtype([("valid", "<u4"), ("kind", "<u4"), ("proto", "<u4"), ("len", "<u4"), ("t", "<i8"),
@@ -275,6 +276,15 @@ def load_library(path: Optional[str] = None):
     lib.sdx_repeat_sources_state_bytes.restype = c_size_t
     lib.sdx_repeat_sources_scratch_bytes.argtypes = [c_int32, c_int32]
     lib.sdx_repeat_sources_scratch_bytes.restype = c_size_t
+    lib.sdx_route_table_create.argtypes = [c_void_p, c_size_t, c_int, POINTER(c_void_p)]
+    lib.sdx_route_table_create.restype = c_int
+    lib.sdx_route_table_destroy.argtypes = [c_void_p]
+    lib.sdx_route_table_destroy.restype = c_int
+    lib.sdx_route_table_lds_routes.argtypes = [c_void_p]
+    lib.sdx_route_table_lds_routes.restype = c_int
+    lib.sdx_route_lines.argtypes = [c_void_p, c_void_p, POINTER(SdxJsonIn), c_int, c_int32, c_void_p, c_int, c_void_p,
+                                    c_void_p, c_void_p, c_void_p]
+    lib.sdx_route_lines.restype = c_int
     lib.sdx_parse_lines.argtypes = [POINTER(SdxLines), POINTER(SdxLinesOut), c_void_p]
     lib.sdx_parse_lines.restype = c_int
     lib.sdx_select_lines.argtypes = [POINTER(SdxLinesOut), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
@@ -370,6 +380,33 @@ def fill_async(dst, stream, value: int = 0) -> None:
         raise ValueError("fill_async: contiguous tensor")
     lib = load_library()
     _check(lib, lib.sdx_fill_async(dst.data_ptr(), int(value), dst.numel() * dst.element_size(), stream.cuda_stream))
+
+
+class DeviceRouteTable:
+    """A route table on the device (sdx_route_table_create): ``handle``, ``table`` (the routes.RouteTable),
+    ``lds_routes`` (how many of its routes the kernel serves from LDS).  A blob the host validator refuses
+    raises RuntimeError and uploads nothing."""
+
+    def __init__(self, eng: "Engine", table):
+        self.lib, self.table = eng.lib, table
+        h = c_void_p()
+        buf = ctypes.create_string_buffer(table.blob, len(table.blob))
+        with eng.torch.cuda.device(eng.device):
+            _check(self.lib, self.lib.sdx_route_table_create(ctypes.cast(buf, c_void_p), len(table.blob), eng.device,
+                                                             ctypes.byref(h)))
+        self.handle = h
+        self.lds_routes = int(self.lib.sdx_route_table_lds_routes(h))
+
+    def close(self):
+        if getattr(self, "handle", None) is not None and self.handle.value:
+            self.lib.sdx_route_table_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Engine:
@@ -811,6 +848,37 @@ class Engine:
         """The compact per-source table mark_repeats_by_source left in ``scratch``: a device uint8 view
         (copy it to the host and read it with REPEAT_SOURCE_ENTRY)."""
         return scratch[16: 16 + REPEAT_SOURCE_ENTRY.itemsize * int(sources)]
+
+    # -- payload routes (sdx_route_lines, DESIGN.md §4l) --------------------------------------------
+    def route_table(self, table) -> "DeviceRouteTable":
+        """``table`` (routes.RouteTable, or a list of (name, pattern) pairs) validated and uploaded
+        (sdx_route_table_create); the handle is kept on the table object, one per device."""
+        from .routes import as_table
+        table = as_table(table)
+        cache = table.__dict__.setdefault("_device", {})
+        if self.device not in cache:
+            cache[self.device] = DeviceRouteTable(self, table)
+        return cache[self.device]
+
+    def alloc_routes(self, n: int, mask: bool = True, skip: bool = True):
+        """{"route": int16[n], "mask": uint64[n] as int64 or None, "skip": uint8[n] or None} for chunks of up to n lines."""
+        t, d, n = self.torch, self.dev, max(int(n), 1)
+        return {"route": t.empty(n, dtype=t.int16, device=d), "mask": t.empty(n, dtype=t.int64, device=d) if mask else None,
+                "skip": t.empty(n, dtype=t.uint8, device=d) if skip else None}
+
+    def route_lines(self, table, json_ins, n: int, route, mask=None, skip=None, repeat=None, drop_unrouted: bool = False,
+                    stream=None) -> None:
+        """sdx_route_lines on ``stream`` (default: the current one; no host sync): route[:n] = the first route
+        of ``table`` (route_table's) whose pattern matches the payload of the line's first record, -1 = none
+        or no result; mask[:n] (optional) one bit per matching route; skip[:n] (optional) = repeat (optional,
+        mark_repeats' mask) or, with ``drop_unrouted``, a result-bearing line without a route -- what
+        launch_json takes as ``skip``.  ``json_ins``: the chunk's SdxJsonIn, one per kind (json_in)."""
+        n = int(n)
+        if not isinstance(table, DeviceRouteTable):
+            table = self.route_table(table)
+        self._mark("route_lines", lambda bank, arr, k, n_, *a: self.lib.sdx_route_lines(bank, table.handle, arr, k, n_, *a),
+                   json_ins, n, [(route, 2 * n), (mask, 8 * n), (skip, n), (repeat, n)],
+                   (_ptr(repeat), 1 if drop_unrouted else 0, _ptr(route), _ptr(mask), _ptr(skip)), stream)
 
     def alloc_json(self, items: int, cap: int):
         t, d = self.torch, self.dev

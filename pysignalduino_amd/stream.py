@@ -33,6 +33,7 @@ unterminated tail into the next call, and gets the chunk's offsets back in stage
 from __future__ import annotations
 
 import collections
+import json
 import os
 from typing import Any, Deque, List, Optional, Sequence, Tuple, Union
 
@@ -162,6 +163,7 @@ class ChunkResult:
         self.wire = self.layout = None
         self.host = {}            # line -> result of the batch API (fallback lines)
         self.repeat = None        # collapse_repeats: uint8[n], 1 = the line repeats the previous result-bearing one
+        self.route = None         # routes: int16[n], the line's route (index into the stream's table), -1 = none / no result
         self.source = None        # repeat_sources: int32[n], the lines' source ids as submitted (a copy)
         self.affix = {}
         # the chunk's text, for line(i): the submitted sequence, or packed (data, offsets), or a
@@ -190,7 +192,7 @@ class ChunkResult:
         self.slot = None
         if isinstance(self.src_data, _ChunkBytes):   # views of the slot's or the caller's pinned memory
             self.src_data, self.src_offsets = self.src_data.copy(), self.src_offsets.copy()
-        for f in ("kind", "status", "off", "len", "wire", "repeat"):
+        for f in ("kind", "status", "off", "len", "wire", "repeat", "route"):
             v = getattr(self, f)
             if isinstance(v, np.ndarray):
                 setattr(self, f, v.copy())
@@ -215,6 +217,12 @@ class ChunkResult:
         d = dict(dev)
         d.update(self.host)
         return [(i, d[i]) for i in sorted(d) if d[i] is not None]
+
+    def items_routed(self) -> List[Tuple[int, int, Union[str, Exception]]]:
+        """items() with every line's route: (line, route, text or ContractError), route -1 = unrouted (a
+        stream with ``routes``)."""
+        route = self.route
+        return [(i, int(route[i]), x) for i, x in self.items()]
 
     def sections(self, k: int):
         offs, nb, T = self.layout
@@ -282,6 +290,9 @@ class _Slot:
         if ls.collapse:   # the repeat pass's buffers: the mask, and the pinned copies the chunk's times / ids go through
             self.rb = ls.repeats.alloc(C, pinned=True)
             self.rep, self.h_times, self.h_src = self.rb.mask, self.rb.h_times, self.rb.h_src
+        if ls.routes is not None:   # the route pass's outputs; its skip mask only where the device drops the unrouted
+            self.rt = eng.alloc_routes(C, mask=False, skip=ls.device_drop)
+            self.h_out = t.empty(self.h_out.numel() + 2 * C + 8, dtype=t.uint8).pin_memory()   # + int16[C] behind the rest
         self.reset()
 
     def reset(self):
@@ -307,7 +318,11 @@ class LineStream:
     sources=)`` and ``submit_packed(..., sources=)`` take one id in [0, S) per line, ``submit_bytes(buf,
     source=)`` one per read buffer -- the stream keeps one carried tail and one last time per source, so
     read buffers of different receivers may be handed over alternately; times need not decrease within a
-    source only.  ChunkResult.source holds the ids beside ``repeat``.
+    source only.  ChunkResult.source holds the ids beside ``repeat``.  ``routes`` (a routes.RouteTable or a list of
+    (name, pattern) pairs) / ``drop_unrouted``: payload routes -- the route pass runs behind the
+    repeat pass and in front of the serialiser, ChunkResult.route holds every line's route, items_routed() the
+    published lines with theirs; with ``drop_unrouted`` a json stream publishes result-bearing, non-repeat,
+    routed lines only (a wire stream's sections are never changed).
 
     submit(lines) -> chunk id; ``submit_packed(data, offsets)`` the same for lines already packed as
     (uint8 bytes, int64 offsets[n + 1]); ``submit_bytes(buf)`` -> chunk ids for a transport's raw read
@@ -317,9 +332,14 @@ class LineStream:
 
     def __init__(self, parser, chunk_lines: int = 250_000, chunk_bytes: Optional[int] = None, output: str = "json",
                  lag: int = 3, collapse_repeats: bool = False, repeat_window: Optional[float] = None,
-                 repeat_sources: Optional[int] = None):
+                 repeat_sources: Optional[int] = None, routes=None, drop_unrouted: bool = False):
         if output not in ("json", "wire"):
             raise ValueError("output must be 'json' or 'wire'")
+        from .routes import as_table
+        self.routes = as_table(routes)    # payload routes; None: no pass, no buffer, no copy
+        self.drop = bool(drop_unrouted)
+        if self.drop and self.routes is None:
+            raise ValueError("drop_unrouted needs routes")
         self.collapse = bool(collapse_repeats)
         from .repeats import window_to_us
         self.window_us = window_to_us(repeat_window)
@@ -347,6 +367,12 @@ class LineStream:
             from .repeats import RepeatPass
             self.repeats = RepeatPass(self.eng, self.window_us, self.n_sources)
             self.rep_ev = None
+        if self.routes is not None:
+            self.dtable = self.eng.route_table(self.routes)
+        # json: the device leaves unrouted lines out of the text buffer -- unless repeats are collapsed: the
+        # host tracker then needs the key of every line that is no repeat, so those texts come back and are
+        # dropped in _collect.  wire: the sections are unchanged, the route only travels beside them
+        self.device_drop = self.drop and output == "json" and not self.collapse
         self.slots = [_Slot(self) for _ in range(self.lag + 1)]
         dev = self.eng.dev
         # the parse at the highest priority: the host waits for chunk k's class counts before it can
@@ -749,6 +775,12 @@ class LineStream:
                 self.repeats.enqueue(s.rb, ins, n, sd)
                 self.rep_ev = t.cuda.Event()
                 self.rep_ev.record(sd)
+            skip = {"skip": s.rep} if self.collapse else {}
+            if self.routes is not None:   # behind the repeat pass, in front of the serialiser
+                ins = [eng.json_in(kd, s.outs[name], lo, n, 2) for name, kd, _, _ in _KINDS if name in s.outs]
+                eng.route_lines(self.dtable, ins, n, s.rt["route"], None, s.rt["skip"], drop_unrouted=self.drop, stream=sd)
+                if s.rt["skip"] is not None:
+                    skip = {"skip": s.rt["skip"]}
             if self.output == "json":
                 jo = s.jout
                 runtime.fill_async(jo["cursor"], sd)
@@ -756,7 +788,7 @@ class LineStream:
                 for name, kd, short, long_ in _KINDS:
                     o = s.outs.get(name)
                     if o is not None and (cnt[short] or (long_ is not None and cnt[long_])):
-                        eng.launch_json(kd, o, lo, n, jo, first_only=2, **({"skip": s.rep} if self.collapse else {}))
+                        eng.launch_json(kd, o, lo, n, jo, first_only=2, **skip)
                 runtime.copy_async(s.h_sizes[:2], jo["cursor"], sd)
                 runtime.copy_async(s.h_sizes[2:], s.cursors.reshape(-1), sd)
             else:
@@ -813,6 +845,10 @@ class LineStream:
             if self.collapse:
                 runtime.copy_async(ho[b + 2 * n: b + 3 * n], s.rep[:n], self.cout)
                 self.d2h_bytes += n + (s.rb.h_read.numel() if s.rb.h_read is not None else 0)
+            if self.routes is not None:
+                s.rp = (b + (3 if self.collapse else 2) * n + 1) & ~1
+                runtime.copy_async(ho[s.rp: s.rp + 2 * n], s.rt["route"][:n].view(t.uint8), self.cout)
+                self.d2h_bytes += 2 * n
             if s.src is not None:   # a submit_bytes chunk: the offsets the device found, for line(i)
                 runtime.copy_async(s.h_offs[: n + 1], lb.offsets[: n + 1], self.cout)
                 self.d2h_bytes += 8 * (n + 1)
@@ -865,12 +901,30 @@ class LineStream:
             res = (self.parser.parse_lines_json(lines) if self.output == "json" else self.parser.parse_lines(lines))
             for i, x in zip(rows, res):
                 r.host[i] = s.bad[i] if i in s.bad else x
+        if self.routes is not None:   # the device's routes; a host-resolved line's from the same tables on the host
+            r.route = ho[s.rp: s.rp + 2 * n].view(np.int16)
+            for i, x in r.host.items():
+                r.route[i] = self._host_route(x)
         if self.collapse:
             self._fix_repeats(s, r, ho[b + 2 * n: b + 3 * n], redo_kinds, kname)
+        if self.drop and self.output == "json":   # published = result-bearing, no repeat, routed
+            if not self.device_drop:
+                r.len[(r.len > 0) & (r.route < 0)] = 0
+            for i, x in r.host.items():           # host rows, and lines republished behind one
+                if isinstance(x, str) and r.route[i] < 0:
+                    r.host[i] = None
         self.done.append(r)
         self.inflight.remove(s)
         s.reset()
         s.stage = 0
+
+    def _host_route(self, x) -> int:
+        """The route of a host-resolved line from its batch-API result (a text, or parse_lines' list)."""
+        if isinstance(x, str):
+            return self.routes.match(json.loads(x)["payload"])[0]
+        if isinstance(x, list) and x:
+            return self.routes.match(x[0].payload)[0]
+        return -1
 
     def _fix_repeats(self, s: _Slot, r: ChunkResult, rep: np.ndarray, redo_kinds, kname) -> None:
         """r.repeat = the chunk's exact mask: the device's, re-decided around the host-resolved rows

@@ -109,9 +109,14 @@ def main():
                     help="with --collapse: stream with repeat_window=SECONDS; the lines get synthetic, evenly spaced "
                          "arrival times (SECONDS / 8 apart, so a burst of --repeat 4 stays inside the window; they run "
                          "on over the passes)")
+    ap.add_argument("--routes", default=None, metavar="LIST", help="stream with payload routes (DESIGN.md §4l): 'default' "
+                    "(routes.DEFAULT_ROUTES) or one regex, which becomes a one-route list")
+    ap.add_argument("--drop-unrouted", action="store_true", help="with --routes: unrouted lines are never serialised")
     args = ap.parse_args()
     if args.window is not None and not args.collapse:
         ap.error("--window needs --collapse")
+    if args.drop_unrouted and args.routes is None:
+        ap.error("--drop-unrouted needs --routes")
     import torch
     from pysignalduino_amd import frontend, runtime, synth
     from pysignalduino_amd.sd_protocols import SDProtocols
@@ -135,6 +140,11 @@ def main():
         src = np.repeat(offsets[:-1][idx] - new_off[:-1], lens) + np.arange(int(new_off[-1]))
         data, offsets = data[src], new_off
     ckw = {"collapse_repeats": True} if args.collapse else {}
+    if args.routes is not None:
+        from pysignalduino_amd import routes as routesmod
+        ckw["routes"] = routesmod.RouteTable(routesmod.DEFAULT_ROUTES if args.routes == "default" else [("only", args.routes)])
+        ckw["drop_unrouted"] = args.drop_unrouted
+    routed = [0, 0, 0]   # --routes: lines routed, JSON bytes copied out, chunks (over all results)
     timed = args.window is not None
     if timed:
         ckw["repeat_window"] = args.window
@@ -208,6 +218,11 @@ def main():
             if timed:
                 marked[0] += int(np.count_nonzero(r.repeat))
                 marked[1] += r.n
+            if r.json is not None:
+                routed[1] += len(r.json)
+                routed[2] += 1
+            if args.routes is not None:
+                routed[0] += int(np.count_nonzero(r.route >= 0))
             if first is None and args.check:
                 first = r.detach()
             if args.bytes and args.check and sum(x.n for x in head) < C:
@@ -217,6 +232,11 @@ def main():
         if timed:
             marked[0] += int(np.count_nonzero(r.repeat))
             marked[1] += r.n
+        if r.json is not None:
+            routed[1] += len(r.json)
+            routed[2] += 1
+        if args.routes is not None:
+            routed[0] += int(np.count_nonzero(r.route >= 0))
         if first is None and args.check:
             first = r.detach()
         if args.bytes and args.check and sum(x.n for x in head) < C:
@@ -248,6 +268,9 @@ def main():
         "repeat": args.repeat, "collapse": bool(args.collapse),
         **({"repeat_window_s": args.window, "time_spacing_us": spacing_us, "repeats_marked": marked[0],
             "lines_seen": marked[1]} if timed else {}),
+        **({"routes": args.routes, "drop_unrouted": bool(args.drop_unrouted), "lines_routed": routed[0]}
+           if args.routes is not None else {}),
+        **({"json_bytes_per_chunk": routed[1] / routed[2]} if routed[2] else {}),
         "output": args.output, "input": "bytes" if args.bytes else "packed", "chunks": nsteps, "ms_per_chunk": 1e3 * per_chunk,
         "kernels_ms_per_chunk": {"parse+select": 1e3 * k_parse, "demod+serialise": 1e3 * k_demod},
         "chunk_span_ms_median": 1e3 * float(np.median(span)),
