@@ -570,6 +570,33 @@ int sdx_route_lines(const sdx_bank* bank, const sdx_route_table* table, const sd
                     const uint8_t* repeat_dev, int drop_unrouted, int16_t* route_dev, uint64_t* mask_dev,
                     uint8_t* skip_dev, void* hip_stream);
 
+/* ---- payload routes over every record of a line ------------------------------------
+ * FHEM dispatches every message a line demodulates to; the telegram goes to the first client that accepts
+ * any of them.  For a result-bearing line whose kind (the lowest kind with SDX_ST_OK and n_rec > 0) has
+ * the records [rec_begin, rec_begin + n_rec): PICK = the smallest i such that some route matches the
+ * payload of record rec_begin + i, 0 when none does; route and mask are those of record pick as above.  A
+ * line without a result has pick 0, route -1, mask 0.
+ * sdx_route_records, one kernel on the caller's stream (record 0 lane = line, then the other records of the
+ * lines still unrouted lane = record): route_dev [n] int16, mask_dev [n] uint64 or NULL, pick_dev [n] uint16, and
+ * view_dev[i] [n] sdx_desc for kinds[i], i in [0, k) -- the PICKED VIEW: for a result-bearing line in its
+ * own kind {rec_begin + pick, 1, SDX_ST_OK, 0}, in every other case (another kind's slot, raised,
+ * overflowed, absent) the input descriptor's bytes.  An sdx_json_in whose desc_dev is a view makes every
+ * first_only 1 / 2 consumer (sdx_serialize_json(_skip), sdx_mark_repeats*, sdx_route_lines) act on the
+ * picked record.  view_dev itself is a host array of k device pointers.  Every entry of the given outputs
+ * in [0, n) is written.  No allocation, no synchronisation, no global atomics, nothing read past a
+ * payload's end.  SDX_EINVAL (nothing launched): what sdx_route_lines refuses, a null pick_dev, a null
+ * view_dev or entry of it, a misaligned pick_dev (2 bytes) or view (4).
+ * sdx_route_skip, one kernel (lane = line): skip_dev[g] = (repeat_dev && repeat_dev[g]) || (drop_unrouted
+ * && result-bearing(g) && route_dev[g] < 0) -- sdx_route_lines' skip mask as a pass of its own, for the
+ * order match, repeat pass over the views, skip.  kinds: only kind, desc_dev and n are read (the launch's
+ * descriptors or a view: the same lines are result-bearing).  SDX_EINVAL: a null route_dev or skip_dev, a
+ * misaligned route_dev, bad kinds, n < 0. */
+int sdx_route_records(const sdx_bank* bank, const sdx_route_table* table, const sdx_json_in* kinds, int k, int32_t n,
+                      int16_t* route_dev, uint64_t* mask_dev, uint16_t* pick_dev, sdx_desc* const* view_dev,
+                      void* hip_stream);
+int sdx_route_skip(const sdx_json_in* kinds, int k, int32_t n, const int16_t* route_dev, const uint8_t* repeat_dev,
+                   int drop_unrouted, uint8_t* skip_dev, void* hip_stream);
+
 /* ---- unit-level entry ------------------------------------------------------------------------
  * The reference's helper methods that its own unit tests call on SDProtocols, evaluated on n
  * independent inputs in one launch (lane = item), with the device code the demodulation kernels

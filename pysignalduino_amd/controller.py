@@ -49,6 +49,8 @@ decoded telegram's payload against an ordered client list on the device (DESIGN.
 to ``<base_topic>/state/messages``; ``drop_unrouted=True`` publishes nothing for a telegram no route
 matches (its text is never built) -- its line keeps its ``_handle_as_command_response`` turn, and it
 starts and breaks runs of repeats as before.  The defaults publish exactly as without routes.
+``route_match="any"``: of a line that demodulates to several messages, the first one that
+some route matches is the telegram -- its text is published, to its client's topic with ``route_topics``.
 """
 from __future__ import annotations
 
@@ -64,12 +66,17 @@ class BatchingParserTask:
                  logger: Optional[logging.Logger] = None, stream: bool = True, lag: int = 3,
                  collapse_repeats: bool = False, repeat_window: Optional[float] = None,
                  clock: Optional[Callable[[], int]] = None, routes=None, drop_unrouted: bool = False,
-                 route_topics: bool = False):
+                 route_topics: bool = False, route_match: str = "first"):
         if publish not in ("objects", "json"):
             raise ValueError("publish must be 'objects' or 'json'")
         # payload routes: the texts' routes come from the device, so they need publish='json'
         from .routes import as_table
         self.routes = as_table(routes)
+        if route_match not in ("first", "any"):
+            raise ValueError(f"route_match must be 'first' or 'any', not {route_match!r}")
+        if route_match == "any" and self.routes is None:
+            raise ValueError("route_match='any' needs routes")
+        self.route_match = route_match
         self.drop_unrouted, self.route_topics = bool(drop_unrouted), bool(route_topics)
         if (self.drop_unrouted or self.route_topics) and self.routes is None:
             raise ValueError("drop_unrouted / route_topics need routes")
@@ -176,7 +183,12 @@ class BatchingParserTask:
         return f"{base}/state/messages"
 
     def _route_kw(self) -> dict:
-        return {} if self.routes is None else {"routes": self.routes, "drop_unrouted": self.drop_unrouted}
+        if self.routes is None:
+            return {}
+        kw = {"routes": self.routes, "drop_unrouted": self.drop_unrouted}
+        if self.route_match != "first":   # "first" calls exactly as before
+            kw["route_match"] = self.route_match
+        return kw
 
     @staticmethod
     def _routed_items(r) -> List[Any]:
@@ -361,7 +373,8 @@ class BatchingParserTask:
         return results
 
     def _parse_routed(self, lines: List[Any]) -> List[Any]:
-        return self.c.parser.parse_lines_routed(lines, self.routes, drop_unrouted=self.drop_unrouted)
+        kw = self._route_kw()
+        return self.c.parser.parse_lines_routed(lines, kw.pop("routes"), **kw)
 
     async def run(self) -> None:
         c = self.c

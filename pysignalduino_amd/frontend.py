@@ -215,6 +215,14 @@ class LineBatch:
                 "flags": self.mcflags, "len": self.dlen, "n": self.n}
 
 
+def _check_route_match(route_match, routes) -> None:
+    """The ``route_match`` argument of parse_lines_routed / stream: "first" or "any", the latter only with routes."""
+    if route_match not in ("first", "any"):
+        raise ValueError(f"route_match must be 'first' or 'any', not {route_match!r}")
+    if route_match == "any" and routes is None:
+        raise ValueError("route_match='any' needs routes")
+
+
 def _contract(i: int, name) -> ContractError:
     """The slot value of a line whose demodulation hit a device limit (SDX_RAISE_CONTRACT): not a
     reference outcome, so it is reported, never turned into an empty result list."""
@@ -547,20 +555,26 @@ class SignalParser:
     # ------------------------------------------------------------------------------------------
     def stream(self, chunk_lines: int = 250_000, chunk_bytes: Optional[int] = None, output: str = "json",
                lag: int = 3, collapse_repeats: bool = False, repeat_window: Optional[float] = None,
-               repeat_sources: Optional[int] = None, routes=None, drop_unrouted: bool = False):
+               repeat_sources: Optional[int] = None, routes=None, drop_unrouted: bool = False,
+               route_match: str = "first"):
         """A pipelined LineStream over this parser (pysignalduino_amd/stream.py): chunks of raw lines
         in, the controller's JSON texts (or the wire form) out, the PCIe copies, parse, demodulation
         and serialisation of successive chunks overlapping; the same per-line results as
         parse_lines_json / parse_lines.  ``repeat_sources``: the stream merges that many receivers, every
         submit names its lines' source ids and repeat suppression runs per source (stream.py).  ``routes``
         (a routes.RouteTable or a list of (name, pattern) pairs) / ``drop_unrouted``: payload routes, as
-        parse_lines_routed: ChunkResult.route and items_routed(); None leaves the stream as it is."""
+        parse_lines_routed: ChunkResult.route and items_routed(); None leaves the stream as it is.
+        ``route_match="any"`` (with ``routes``): the line's first message that a route wants is the published
+        one; ChunkResult.pick holds its index."""
         from .stream import LineStream
         kw = {} if repeat_window is None else {"repeat_window": repeat_window}
         if repeat_sources is not None:
             kw["repeat_sources"] = repeat_sources
+        _check_route_match(route_match, routes)
         if routes is not None:
             kw.update(routes=routes, drop_unrouted=drop_unrouted)
+            if route_match != "first":
+                kw["route_match"] = route_match
         elif drop_unrouted:
             raise ValueError("drop_unrouted needs routes")
         return LineStream(self, chunk_lines=chunk_lines, chunk_bytes=chunk_bytes, output=output, lag=lag,
@@ -592,7 +606,7 @@ class SignalParser:
 
     def parse_lines_routed(self, lines: Sequence[Union[str, bytes]], routes, drop_unrouted: bool = False,
                            collapse_repeats: bool = False, times=None, repeat_window: Optional[float] = None,
-                           sources=None) -> List[Union[None, Tuple[int, str], Exception]]:
+                           sources=None, route_match: str = "first") -> List[Union[None, Tuple[int, str], Exception]]:
         """parse_lines_json with payload routes: per line None, or (route_index, text) -- the
         text parse_lines_json gives, and the index of the first route of ``routes`` (a routes.RouteTable or
         a list of (name, pattern) pairs) whose pattern matches the payload of ``decoded[0]`` by ``re.search``,
@@ -600,26 +614,36 @@ class SignalParser:
         front of the serialiser; host-resolved lines are matched with RouteTable.match.  ``drop_unrouted``:
         an unrouted line gives None (published = result-bearing, no repeat, routed); routing never changes
         which lines are repeats.  The other arguments, and ContractError slots, as parse_lines_json.  The
-        lines' routes are left in ``last_routes`` (int16, -1 also for lines without a result)."""
+        lines' routes are left in ``last_routes`` (int16, -1 also for lines without a result).
+        ``route_match="any"``: FHEM's answer for a line that demodulates to several messages --
+        the published message is the first one, in the reference's list order, that some route matches
+        (``decoded[0]`` when none does): its text, its repeat key and its route, matched on the device over
+        every record of the line (sdx_route_records).  ``last_picks`` (uint16) holds that message's index;
+        "first" leaves it None."""
         from .routes import as_table
+        _check_route_match(route_match, routes)
         table = as_table(routes)
         if table is None:
             raise ValueError("parse_lines_routed needs a route table")
+        any_ = route_match == "any"
         sources = self._source_args(collapse_repeats, sources, len(lines))
         times, w = self._window_args(collapse_repeats, times, repeat_window, len(lines), sources)
         if len(lines) == 0:
             if collapse_repeats:
                 self.last_repeat_mask = np.zeros(0, np.uint8)
             self.last_routes = np.zeros(0, np.int16)
+            self.last_picks = np.zeros(0, np.uint16) if any_ else None
             return []
         data, offsets, bad = pack_lines(lines)
         return self._texts(lines, LineBatch(self.protocols._ensure(), data, offsets), bad, len(data), collapse_repeats,
-                           times, w, sources, routes=table, drop_unrouted=drop_unrouted)
+                           times, w, sources, routes=table, drop_unrouted=drop_unrouted, match_any=any_)
 
     def _texts(self, lines, lb: LineBatch, bad: dict, nbytes: int, collapse: bool = False, times=None,
-               window_us: Optional[int] = None, sources=None, routes=None, drop_unrouted: bool = False):
+               window_us: Optional[int] = None, sources=None, routes=None, drop_unrouted: bool = False,
+               match_any: bool = False):
         """parse_lines_json from the uploaded batch on (``lines`` and ``nbytes`` as in _objects).  ``routes``
-        (a routes.RouteTable; parse_lines_routed): every text becomes (route, text), see there."""
+        (a routes.RouteTable; parse_lines_routed): every text becomes (route, text), see there; ``match_any``:
+        its route_match="any"."""
         n = len(lines)
         eng = self.protocols._ensure()
         bk = self.protocols._bank
@@ -701,6 +725,7 @@ class SignalParser:
 
         rep = np.zeros(n, np.uint8)   # the device's repeat mask (collapse)
         route = np.full(n, -1, np.int16)   # the lines' routes (routes)
+        pick = np.zeros(n, np.uint16)      # the lines' picked records (match_any)
         if collapse:
             from .repeats import RepeatPass, apply_mask, count_sources, objects_key, text_key
             rpass = RepeatPass(eng, window_us, None if sources is None else count_sources(sources))
@@ -730,11 +755,22 @@ class SignalParser:
             if kept:   # a fresh stream of lines per call; nothing is read back but the mask (and the sources' table)
                 ins = [eng.json_in(kind, out, lo, n) for kind, out, _ in kept]
                 skip = None
+                if match_any:
+                    # the match first: it picks every line's published record and writes the views in which a
+                    # line owns exactly that record; the repeat pass and the serialiser then run over the views
+                    rb = eng.alloc_routes(n, mask=False, skip=not collapse and drop_unrouted, pick=True, views=len(ins))
+                    eng.route_records(eng.route_table(routes), ins, n, rb["route"], rb["pick"], rb["views"])
+                    ins = [eng.json_in_view(ji, v) for ji, v in zip(ins, rb["views"])]
+                    kept = [(kind, dict(out, desc=v), json_cap) for (kind, out, json_cap), v in zip(kept, rb["views"])]
                 if collapse:
                     rbufs = rpass.alloc(n, pinned=False)
                     rpass.enqueue(rbufs, ins, n, times=times, sources=sources)
                     skip = rbufs.mask
-                if routes is not None:
+                if match_any:
+                    if rb["skip"] is not None:   # as below: with collapse the unrouted texts still come back
+                        eng.route_skip(ins, n, rb["route"], rb["skip"], drop_unrouted=True)
+                        skip = rb["skip"]
+                elif routes is not None:
                     # behind the repeat pass, in front of the serialiser.  With collapse the host needs the key
                     # of every line that is no repeat (RepeatTracker), so unrouted texts still come back and are
                     # dropped below; without it the device leaves them out
@@ -747,6 +783,8 @@ class SignalParser:
                     rep = rbufs.mask[:n].cpu().numpy()
                 if routes is not None:
                     route = rb["route"][:n].cpu().numpy()
+                if match_any:
+                    pick = rb["pick"][:n].cpu().numpy().view(np.uint16)
             jobs = []
         for kind, rec_cap, heap_cap, json_cap, launches in jobs:
             for _attempt in range(4):
@@ -784,6 +822,9 @@ class SignalParser:
         host_keys = {}   # collapse: the host-resolved rows' keys (None: no result)
         if grows:  # general-path lines (rare): their objects through parse_lines, the text as _message_to_json
             for i, g in zip(grows, self.parse_lines([lines[i] for i in grows])):
+                if match_any and isinstance(g, list) and g:   # the published message is the picked one
+                    pick[i], route[i], _ = routes.pick([m.payload for m in g])
+                    g = g[int(pick[i]): int(pick[i]) + 1]
                 if collapse:
                     host_keys[i] = objects_key(g)
                 if exact[i]:
@@ -795,7 +836,7 @@ class SignalParser:
                 elif g:
                     texts[i] = json.dumps({"protocol_id": g[0].protocol_id, "payload": g[0].payload,
                                            "metadata": g[0].metadata}, indent=4)
-                    if routes is not None:   # a host-resolved line: the same tables, walked on the host
+                    if routes is not None and not match_any:   # a host-resolved line: the same tables, walked on the host
                         route[i] = routes.match(g[0].payload)[0]
         for i in range(n):
             if i in bad:
@@ -806,8 +847,14 @@ class SignalParser:
         if collapse:
             fetched = {}
 
+            def one_text(i):    # the line's published text on its own (match_any: the picked message's)
+                if not match_any:
+                    return self.parse_lines_json([lines[i]])[0]
+                x = self.parse_lines_routed([lines[i]], routes, route_match="any")[0]
+                return x[1] if isinstance(x, tuple) else x
+
             def fetch_key(i):   # a flagged line whose run head the host does not know: the batch API
-                fetched[i] = self.parse_lines_json([lines[i]])[0]
+                fetched[i] = one_text(i)
                 return text_key(_KIND_NAME[int(kinds[i])], fetched[i]) if isinstance(fetched[i], str) else None
 
             dev_key_of = lambda i: text_key(_KIND_NAME[int(kinds[i])], texts[i])   # noqa: E731
@@ -818,11 +865,12 @@ class SignalParser:
                 texts[i] = None
 
             def republish(i):    # the device skipped it, but its predecessor was a host row
-                texts[i] = fetched[i] if i in fetched else self.parse_lines_json([lines[i]])[0]
+                texts[i] = fetched[i] if i in fetched else one_text(i)
             apply_mask(mask, rep, host_keys, drop, republish)
             self.last_repeat_mask = mask
         if routes is not None:
             self.last_routes = route
+            self.last_picks = pick if match_any else None
             for i, x in enumerate(texts):
                 if isinstance(x, str):
                     texts[i] = None if drop_unrouted and route[i] < 0 else (int(route[i]), x)

@@ -133,6 +133,16 @@ class RouteTable:
                 mask |= 1 << r
         return ((mask & -mask).bit_length() - 1 if mask else -1), mask
 
+    def pick(self, payloads: Sequence[Union[str, bytes]]) -> Tuple[int, int, int]:
+        """(pick, route, mask) of a line's payloads in the reference's list order: pick = the
+        index of the first payload some route matches, route and mask that payload's; (0, -1, 0) when none
+        matches or the list is empty.  The host restatement of sdx_route_records."""
+        for i, payload in enumerate(payloads):
+            route, mask = self.match(payload)
+            if route >= 0:
+                return i, route, mask
+        return 0, -1, 0
+
     def name_of(self, route: int):
         """The route's name, None for -1."""
         return self.names[route] if route >= 0 else None

@@ -51,7 +51,7 @@ EXPORTED = ["sdx_abi_version", "sdx_last_error", "sdx_source_hash", "sdx_layout_
             "sdx_repeat_scratch_bytes", "sdx_repeat_tile", "sdx_mark_repeats_timed", "sdx_repeat_timed_state_bytes",
             "sdx_repeat_timed_scratch_bytes", "sdx_mark_repeats_by_source", "sdx_repeat_sources_state_bytes",
             "sdx_repeat_sources_scratch_bytes", "sdx_route_table_create", "sdx_route_table_destroy",
-            "sdx_route_table_lds_routes", "sdx_route_lines"]
+            "sdx_route_table_lds_routes", "sdx_route_lines", "sdx_route_records", "sdx_route_skip"]
 REPEAT_SOURCES_MAX = 4096   # SDX_REPEAT_SOURCES_MAX
 # sdx_repeat_source_entry (csrc/sdx_repeat_layout.h): a source's slot header after a chunk + its last result-bearing line
 REPEAT_SOURCE_ENTRY = np.dtype([("valid", "<u4"), ("kind", "<u4"), ("proto", "<u4"), ("len", "<u4"), ("t", "<i8"),
@@ -285,6 +285,11 @@ def load_library(path: Optional[str] = None):
     lib.sdx_route_lines.argtypes = [c_void_p, c_void_p, POINTER(SdxJsonIn), c_int, c_int32, c_void_p, c_int, c_void_p,
                                     c_void_p, c_void_p, c_void_p]
     lib.sdx_route_lines.restype = c_int
+    lib.sdx_route_records.argtypes = [c_void_p, c_void_p, POINTER(SdxJsonIn), c_int, c_int32, c_void_p, c_void_p, c_void_p,
+                                      POINTER(c_void_p), c_void_p]
+    lib.sdx_route_records.restype = c_int
+    lib.sdx_route_skip.argtypes = [POINTER(SdxJsonIn), c_int, c_int32, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+    lib.sdx_route_skip.restype = c_int
     lib.sdx_parse_lines.argtypes = [POINTER(SdxLines), POINTER(SdxLinesOut), c_void_p]
     lib.sdx_parse_lines.restype = c_int
     lib.sdx_select_lines.argtypes = [POINTER(SdxLinesOut), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
@@ -860,11 +865,27 @@ class Engine:
             cache[self.device] = DeviceRouteTable(self, table)
         return cache[self.device]
 
-    def alloc_routes(self, n: int, mask: bool = True, skip: bool = True):
-        """{"route": int16[n], "mask": uint64[n] as int64 or None, "skip": uint8[n] or None} for chunks of up to n lines."""
+    def alloc_routes(self, n: int, mask: bool = True, skip: bool = True, pick: bool = False, views: int = 0):
+        """{"route": int16[n], "mask": uint64[n] as int64 or None, "skip": uint8[n] or None} for chunks of up to n lines;
+        ``pick`` / ``views`` = k add route_records' outputs: "pick" uint16[n] (as int16) and "views", k descriptor
+        arrays of 8 n bytes each (uint8)."""
         t, d, n = self.torch, self.dev, max(int(n), 1)
-        return {"route": t.empty(n, dtype=t.int16, device=d), "mask": t.empty(n, dtype=t.int64, device=d) if mask else None,
-                "skip": t.empty(n, dtype=t.uint8, device=d) if skip else None}
+        b = {"route": t.empty(n, dtype=t.int16, device=d), "mask": t.empty(n, dtype=t.int64, device=d) if mask else None,
+             "skip": t.empty(n, dtype=t.uint8, device=d) if skip else None}
+        if pick:
+            b["pick"] = t.empty(n, dtype=t.int16, device=d)
+        if views:
+            b["views"] = [t.empty(8 * n, dtype=t.uint8, device=d) for _ in range(int(views))]
+        return b
+
+    @staticmethod
+    def json_in_view(ji: SdxJsonIn, view) -> SdxJsonIn:
+        """``ji`` with desc_dev replaced by ``view`` (one of route_records' descriptor arrays): every first_only
+        consumer then acts on the line's picked record."""
+        out = SdxJsonIn()
+        ctypes.memmove(ctypes.byref(out), ctypes.byref(ji), ctypes.sizeof(SdxJsonIn))
+        out.desc_dev = _ptr(view)
+        return out
 
     def route_lines(self, table, json_ins, n: int, route, mask=None, skip=None, repeat=None, drop_unrouted: bool = False,
                     stream=None) -> None:
@@ -879,6 +900,29 @@ class Engine:
         self._mark("route_lines", lambda bank, arr, k, n_, *a: self.lib.sdx_route_lines(bank, table.handle, arr, k, n_, *a),
                    json_ins, n, [(route, 2 * n), (mask, 8 * n), (skip, n), (repeat, n)],
                    (_ptr(repeat), 1 if drop_unrouted else 0, _ptr(route), _ptr(mask), _ptr(skip)), stream)
+
+    def route_records(self, table, json_ins, n: int, route, pick, views, mask=None, stream=None) -> None:
+        """sdx_route_records on ``stream`` (default: the current one; no host sync): pick[:n] = the
+        index of the line's first record that some route of ``table`` matches (0: none, or no result), route[:n]
+        / mask[:n] (optional) that record's; views[i][:8 n] = json_ins[i]'s descriptors with every result-bearing
+        line owning exactly its picked record (json_in_view)."""
+        n = int(n)
+        if not isinstance(table, DeviceRouteTable):
+            table = self.route_table(table)
+        if len(views) != len(json_ins):
+            raise ValueError("route_records: one view per kind")
+        varr = (c_void_p * max(len(views), 1))(*[_ptr(v) for v in views])
+        self._mark("route_records", lambda bank, arr, k, n_, *a: self.lib.sdx_route_records(bank, table.handle, arr, k, n_, *a),
+                   json_ins, n, [(route, 2 * n), (mask, 8 * n), (pick, 2 * n)] + [(v, 8 * n) for v in views],
+                   (_ptr(route), _ptr(mask), _ptr(pick), varr), stream)
+
+    def route_skip(self, json_ins, n: int, route, skip, repeat=None, drop_unrouted: bool = False, stream=None) -> None:
+        """sdx_route_skip on ``stream``: skip[:n] = repeat (optional, mark_repeats' mask) or, with ``drop_unrouted``,
+        a result-bearing line whose route[:n] entry is negative -- what launch_json takes as ``skip``."""
+        n = int(n)
+        self._mark("route_skip", lambda bank, arr, k, n_, *a: self.lib.sdx_route_skip(arr, k, n_, *a),
+                   json_ins, n, [(route, 2 * n), (skip, n), (repeat, n)],
+                   (_ptr(route), _ptr(repeat), 1 if drop_unrouted else 0, _ptr(skip)), stream)
 
     def alloc_json(self, items: int, cap: int):
         t, d = self.torch, self.dev

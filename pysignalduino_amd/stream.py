@@ -164,6 +164,7 @@ class ChunkResult:
         self.host = {}            # line -> result of the batch API (fallback lines)
         self.repeat = None        # collapse_repeats: uint8[n], 1 = the line repeats the previous result-bearing one
         self.route = None         # routes: int16[n], the line's route (index into the stream's table), -1 = none / no result
+        self.pick = None          # route_match="any": uint16[n], the index of the line's published message
         self.source = None        # repeat_sources: int32[n], the lines' source ids as submitted (a copy)
         self.affix = {}
         # the chunk's text, for line(i): the submitted sequence, or packed (data, offsets), or a
@@ -192,7 +193,7 @@ class ChunkResult:
         self.slot = None
         if isinstance(self.src_data, _ChunkBytes):   # views of the slot's or the caller's pinned memory
             self.src_data, self.src_offsets = self.src_data.copy(), self.src_offsets.copy()
-        for f in ("kind", "status", "off", "len", "wire", "repeat", "route"):
+        for f in ("kind", "status", "off", "len", "wire", "repeat", "route", "pick"):
             v = getattr(self, f)
             if isinstance(v, np.ndarray):
                 setattr(self, f, v.copy())
@@ -291,8 +292,10 @@ class _Slot:
             self.rb = ls.repeats.alloc(C, pinned=True)
             self.rep, self.h_times, self.h_src = self.rb.mask, self.rb.h_times, self.rb.h_src
         if ls.routes is not None:   # the route pass's outputs; its skip mask only where the device drops the unrouted
-            self.rt = eng.alloc_routes(C, mask=False, skip=ls.device_drop)
-            self.h_out = t.empty(self.h_out.numel() + 2 * C + 8, dtype=t.uint8).pin_memory()   # + int16[C] behind the rest
+            extra = {"pick": True, "views": len(self.outs)} if ls.match_any else {}   # "first": the call as it was
+            self.rt = eng.alloc_routes(C, mask=False, skip=ls.device_drop, **extra)
+            # + int16[C] behind the rest (route_match="any": + uint16[C], the picks)
+            self.h_out = t.empty(self.h_out.numel() + (4 if ls.match_any else 2) * C + 8, dtype=t.uint8).pin_memory()
         self.reset()
 
     def reset(self):
@@ -322,7 +325,9 @@ class LineStream:
     (name, pattern) pairs) / ``drop_unrouted``: payload routes -- the route pass runs behind the
     repeat pass and in front of the serialiser, ChunkResult.route holds every line's route, items_routed() the
     published lines with theirs; with ``drop_unrouted`` a json stream publishes result-bearing, non-repeat,
-    routed lines only (a wire stream's sections are never changed).
+    routed lines only (a wire stream's sections are never changed).  ``route_match="any"``: the
+    line's first message that a route matches is the published one -- the match runs first (sdx_route_records), the
+    repeat pass and the serialiser over its picked views; ChunkResult.pick holds the message's index.
 
     submit(lines) -> chunk id; ``submit_packed(data, offsets)`` the same for lines already packed as
     (uint8 bytes, int64 offsets[n + 1]); ``submit_bytes(buf)`` -> chunk ids for a transport's raw read
@@ -332,9 +337,13 @@ class LineStream:
 
     def __init__(self, parser, chunk_lines: int = 250_000, chunk_bytes: Optional[int] = None, output: str = "json",
                  lag: int = 3, collapse_repeats: bool = False, repeat_window: Optional[float] = None,
-                 repeat_sources: Optional[int] = None, routes=None, drop_unrouted: bool = False):
+                 repeat_sources: Optional[int] = None, routes=None, drop_unrouted: bool = False,
+                 route_match: str = "first"):
         if output not in ("json", "wire"):
             raise ValueError("output must be 'json' or 'wire'")
+        from .frontend import _check_route_match
+        _check_route_match(route_match, routes)
+        self.match_any = route_match == "any"
         from .routes import as_table
         self.routes = as_table(routes)    # payload routes; None: no pass, no buffer, no copy
         self.drop = bool(drop_unrouted)
@@ -765,18 +774,31 @@ class LineStream:
                         eng.launch_pulses(kd, pb, s.outs[name], sel=sels[long_], long_variant=True)
             s.cnt = cnt
             lo = {"meta": lb.meta, "pat_val": lb.pat_val, "cp_slot": lb.cp_slot}
+            if self.match_any:
+                # every line's published record and the views in which it owns exactly that one;
+                # nothing of this waits for the previous chunk
+                ins = [eng.json_in(kd, s.outs[name], lo, n, 2) for name, kd, _, _ in _KINDS if name in s.outs]
+                eng.route_records(self.dtable, ins, n, s.rt["route"], s.rt["pick"], s.rt["views"], stream=sd)
+                vins = [eng.json_in_view(ji, v) for ji, v in zip(ins, s.rt["views"])]
             if self.collapse:
                 # only these small kernels wait for the previous chunk (its state pass, on the other
                 # demodulation stream); this chunk's demodulation above is already enqueued beside it
                 if self.rep_ev is not None:
                     sd.wait_event(self.rep_ev)
-                ins = [eng.json_in(kd, s.outs[name], lo, n, 2) for name, kd, _, _ in _KINDS if name in s.outs]
+                ins = vins if self.match_any else [eng.json_in(kd, s.outs[name], lo, n, 2)
+                                                   for name, kd, _, _ in _KINDS if name in s.outs]
                 # the chunk's times and ids came up with its bytes (stage A, in front of the parse)
                 self.repeats.enqueue(s.rb, ins, n, sd)
                 self.rep_ev = t.cuda.Event()
                 self.rep_ev.record(sd)
             skip = {"skip": s.rep} if self.collapse else {}
-            if self.routes is not None:   # behind the repeat pass, in front of the serialiser
+            jouts = s.outs
+            if self.match_any:   # the match came first; the serialiser reads the picked views
+                jouts = {name: dict(s.outs[name], desc=v) for name, v in zip(s.outs, s.rt["views"])}
+                if s.rt["skip"] is not None:
+                    eng.route_skip(vins, n, s.rt["route"], s.rt["skip"], drop_unrouted=True, stream=sd)
+                    skip = {"skip": s.rt["skip"]}
+            elif self.routes is not None:   # behind the repeat pass, in front of the serialiser
                 ins = [eng.json_in(kd, s.outs[name], lo, n, 2) for name, kd, _, _ in _KINDS if name in s.outs]
                 eng.route_lines(self.dtable, ins, n, s.rt["route"], None, s.rt["skip"], drop_unrouted=self.drop, stream=sd)
                 if s.rt["skip"] is not None:
@@ -786,7 +808,7 @@ class LineStream:
                 runtime.fill_async(jo["cursor"], sd)
                 runtime.fill_async(jo["len"][:n], sd)
                 for name, kd, short, long_ in _KINDS:
-                    o = s.outs.get(name)
+                    o = jouts.get(name)
                     if o is not None and (cnt[short] or (long_ is not None and cnt[long_])):
                         eng.launch_json(kd, o, lo, n, jo, first_only=2, **skip)
                 runtime.copy_async(s.h_sizes[:2], jo["cursor"], sd)
@@ -849,6 +871,9 @@ class LineStream:
                 s.rp = (b + (3 if self.collapse else 2) * n + 1) & ~1
                 runtime.copy_async(ho[s.rp: s.rp + 2 * n], s.rt["route"][:n].view(t.uint8), self.cout)
                 self.d2h_bytes += 2 * n
+                if self.match_any:
+                    runtime.copy_async(ho[s.rp + 2 * n: s.rp + 4 * n], s.rt["pick"][:n].view(t.uint8), self.cout)
+                    self.d2h_bytes += 2 * n
             if s.src is not None:   # a submit_bytes chunk: the offsets the device found, for line(i)
                 runtime.copy_async(s.h_offs[: n + 1], lb.offsets[: n + 1], self.cout)
                 self.d2h_bytes += 8 * (n + 1)
@@ -898,13 +923,27 @@ class LineStream:
         if rows:
             rows = sorted(rows)
             lines = [self._line(s, i) for i in rows]
-            res = (self.parser.parse_lines_json(lines) if self.output == "json" else self.parser.parse_lines(lines))
+            host_picks = None
+            if self.match_any and self.output == "json":   # the picked messages' texts, with their routes and picks
+                res = [x[1] if isinstance(x, tuple) else x
+                       for x in self.parser.parse_lines_routed(lines, self.routes, route_match="any")]
+                host_picks = dict(zip(rows, zip(self.parser.last_picks.tolist(), self.parser.last_routes.tolist())))
+            else:
+                res = (self.parser.parse_lines_json(lines) if self.output == "json" else self.parser.parse_lines(lines))
             for i, x in zip(rows, res):
                 r.host[i] = s.bad[i] if i in s.bad else x
         if self.routes is not None:   # the device's routes; a host-resolved line's from the same tables on the host
             r.route = ho[s.rp: s.rp + 2 * n].view(np.int16)
-            for i, x in r.host.items():
-                r.route[i] = self._host_route(x)
+            if self.match_any:
+                r.pick = ho[s.rp + 2 * n: s.rp + 4 * n].view(np.uint16)
+                for i, x in r.host.items():
+                    if self.output == "json":
+                        r.pick[i], r.route[i] = host_picks[i] if isinstance(x, str) else (0, -1)
+                    else:
+                        r.pick[i], r.route[i], _ = self.routes.pick([m.payload for m in x] if isinstance(x, list) else [])
+            else:
+                for i, x in r.host.items():
+                    r.route[i] = self._host_route(x)
         if self.collapse:
             self._fix_repeats(s, r, ho[b + 2 * n: b + 3 * n], redo_kinds, kname)
         if self.drop and self.output == "json":   # published = result-bearing, no repeat, routed
@@ -932,14 +971,21 @@ class LineStream:
         from .repeats import apply_mask, objects_key, text_key
         n, kind, js = r.n, r.kind, self.output == "json"
         name_of = lambda i: kname.get(int(kind[i]), "?")   # noqa: E731
-        host_keys = {i: ((text_key(name_of(i), x) if isinstance(x, str) else None) if js else objects_key(x))
+        picked = lambda i, x: x[int(r.pick[i]): int(r.pick[i]) + 1] if r.pick is not None and isinstance(x, list) else x   # noqa: E731
+        host_keys = {i: ((text_key(name_of(i), x) if isinstance(x, str) else None) if js else objects_key(picked(i, x)))
                      for i, x in r.host.items()}
         redo = [i for i in r.host if redo_kinds and kname.get(int(kind[i])) in redo_kinds
                 and r.status[i] == runtime.LS_OK]
         fetched = {}
 
+        def one_text(i):       # the line's published text on its own (route_match="any": the picked message's)
+            if not self.match_any:
+                return self.parser.parse_lines_json([self._line(s, i)])[0]
+            x = self.parser.parse_lines_routed([self._line(s, i)], self.routes, route_match="any")[0]
+            return x[1] if isinstance(x, tuple) else x
+
         def fetch(i):
-            fetched[i] = self.parser.parse_lines_json([self._line(s, i)])[0]
+            fetched[i] = one_text(i)
             return text_key(name_of(i), fetched[i]) if isinstance(fetched[i], str) else None
 
         if js:
@@ -965,7 +1011,7 @@ class LineStream:
                 r.len[i] = 0           # a repeat of a host-resolved line: its text is not published
 
         def republish(i):              # skipped on the device, but its predecessor was a host row
-            r.host[i] = fetched[i] if i in fetched else self.parser.parse_lines_json([self._line(s, i)])[0]
+            r.host[i] = fetched[i] if i in fetched else one_text(i)
         apply_mask(mask, rep, host_keys, drop, republish)
 
     def _wire_keys(self, r: ChunkResult):
@@ -985,7 +1031,7 @@ class LineStream:
             if name not in cache:
                 cache[name] = r.decode(names.index(name))
             desc, rec, heap = cache[name]
-            x = rec[int(desc["rec_begin"][i])]
+            x = rec[int(desc["rec_begin"][i]) + (0 if r.pick is None else int(r.pick[i]))]
             o = int(x["payload_off"])
             return (name, str(tabs[name][int(x["proto"])]), heap[o: o + int(x["payload_len"])].tobytes().decode("latin-1"))
         return has, key_of

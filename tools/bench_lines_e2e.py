@@ -112,11 +112,15 @@ def main():
     ap.add_argument("--routes", default=None, metavar="LIST", help="stream with payload routes (DESIGN.md §4l): 'default' "
                     "(routes.DEFAULT_ROUTES) or one regex, which becomes a one-route list")
     ap.add_argument("--drop-unrouted", action="store_true", help="with --routes: unrouted lines are never serialised")
+    ap.add_argument("--route-match", default="first", choices=("first", "any"), help="with --routes: 'any' publishes a "
+                    "line's first message that a route matches (DESIGN.md §4m)")
     args = ap.parse_args()
     if args.window is not None and not args.collapse:
         ap.error("--window needs --collapse")
     if args.drop_unrouted and args.routes is None:
         ap.error("--drop-unrouted needs --routes")
+    if args.route_match != "first" and args.routes is None:
+        ap.error("--route-match any needs --routes")
     import torch
     from pysignalduino_amd import frontend, runtime, synth
     from pysignalduino_amd.sd_protocols import SDProtocols
@@ -144,6 +148,8 @@ def main():
         from pysignalduino_amd import routes as routesmod
         ckw["routes"] = routesmod.RouteTable(routesmod.DEFAULT_ROUTES if args.routes == "default" else [("only", args.routes)])
         ckw["drop_unrouted"] = args.drop_unrouted
+        if args.route_match != "first":
+            ckw["route_match"] = args.route_match
     routed = [0, 0, 0]   # --routes: lines routed, JSON bytes copied out, chunks (over all results)
     timed = args.window is not None
     if timed:
@@ -268,7 +274,8 @@ def main():
         "repeat": args.repeat, "collapse": bool(args.collapse),
         **({"repeat_window_s": args.window, "time_spacing_us": spacing_us, "repeats_marked": marked[0],
             "lines_seen": marked[1]} if timed else {}),
-        **({"routes": args.routes, "drop_unrouted": bool(args.drop_unrouted), "lines_routed": routed[0]}
+        **({"routes": args.routes, "drop_unrouted": bool(args.drop_unrouted), "route_match": args.route_match,
+            "lines_routed": routed[0]}
            if args.routes is not None else {}),
         **({"json_bytes_per_chunk": routed[1] / routed[2]} if routed[2] else {}),
         "output": args.output, "input": "bytes" if args.bytes else "packed", "chunks": nsteps, "ms_per_chunk": 1e3 * per_chunk,
