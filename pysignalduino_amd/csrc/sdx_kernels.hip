@@ -233,10 +233,10 @@ int sdx_gprof_read(unsigned long long* out256, int reset) {
   }
   return SDX_OK;
 }
-int sdx_prof_read(unsigned long long* out32, int reset) {
-  HIPCHK(hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_prof), sizeof(unsigned long long) * 32));
+int sdx_prof_read(unsigned long long* out34, int reset) {
+  HIPCHK(hipMemcpyFromSymbol(out34, HIP_SYMBOL(g_prof), sizeof(unsigned long long) * 34));
   if (reset) {
-    unsigned long long z[32] = {0};
+    unsigned long long z[34] = {0};
     HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_prof), z, sizeof z));
   }
   return SDX_OK;

@@ -28,7 +28,7 @@
 __device__ unsigned long long g_wgt[2 * 65536];
 #endif
 #ifdef SDX_PROF
-__device__ unsigned long long g_prof[32];
+__device__ unsigned long long g_prof[34];  // 0-26, 32-33: the tile's slots; 27-31: k_mc's
 __device__ unsigned long long g_gprof[2][128];  // per MU clock group / MS protocol: wave-cycles, grabs
 #define PROF_T(v) unsigned long long v = __builtin_amdgcn_s_memtime()
 #define PROF_ADD(slot, v)                                                                   \
@@ -198,7 +198,8 @@ struct TileLds {
   int nsurv;
   MsDesc msdesc[LM == 2 ? MS_DESC_LDS : 1];
 #ifdef SDX_PROF
-  unsigned int prof[LM != 0 ? LANE_WAVES : 4][28];  // s_memtime deltas per wave (< 2^32 per kernel)
+  // s_memtime deltas per wave (< 2^32 per kernel); slots 27 and 28 are g_prof's 32 and 33
+  unsigned int prof[LM != 0 ? LANE_WAVES : 4][29];
 #endif
 };
 
@@ -690,6 +691,12 @@ SDX_DEV uint64_t hex8(uint64_t x, int cnt) {
   return cnt >= 8 ? x : x & ((1ull << (8 * cnt)) - 1);
 }
 
+// 8 bits (bit i of x; its higher bits are zero) -> 8 bytes of 0 / 1 (byte i)
+SDX_DEV uint64_t bits8(uint64_t x) {
+  x = (x * 0x0101010101010101ull) & 0x8040201008040201ull;  // byte i holds bit i, at its own position
+  return ((x + 0x7F7F7F7F7F7F7F7Full) >> 7) & 0x0101010101010101ull;
+}
+
 // pattern_lookup (message_unsynced.py:113-123): U = every unit occurrence; V1 / VF = occurrences
 // whose symbol is '1' / 'F' (the LAST writer of an identical unit string decides its symbol)
 template <int NW>
@@ -862,6 +869,23 @@ SDX_DEV void finish_mu_lane(T& L, const sdx_out& out, int wave, const BankView& 
       const int cnt = (dlen - t < 8) ? dlen - t : 8;
       w.put(hex8(x & 0xFFFFFFFFull, cnt), cnt);
     }
+  } else if (binm && !usearr) {
+    // binary dispatch from the packed words, 8 characters per step: t is a multiple of 8, so the 8
+    // bits lie in one word; bits at or past nb are clear in P1 and PF, so padding comes out as '0'
+    PROF_T(t_bd);
+    for (int t = 0; t < dlen; t += 8) {
+      const int wi = t >> 6, sh = t & 63;
+      uint64_t x = 0x3030303030303030ull + bits8((m_word(P1, wi) >> sh) & 0xFFull);
+      if (anyf) {
+        const uint64_t f = bits8((m_word(PF, wi) >> sh) & 0xFFull) * 0xFFull;
+        x = (x & ~f) | (0x4646464646464646ull & f);  // 'F'
+      }
+      const int cnt = (dlen - t < 8) ? dlen - t : 8;
+      w.put(cnt >= 8 ? x : x & ((1ull << (8 * cnt)) - 1), cnt);
+    }
+    PROF_ADDD(27, t_bd);
+  } else if (!usearr) {  // anyf without binary dispatch: f"{None}"
+    w.put(0x656E6F4Eull, 4);
   } else {
     for (int i = 0; i < dlen; ++i) w.put(dchar(i), 1);
   }
@@ -1368,6 +1392,9 @@ SDX_DEV void flush_tile(TileLds<NW, TM, LM>& L, const int* msg_of, int nvalid, c
                         int kind) {
   using T = TileLds<NW, TM, LM>;
   const int tid = threadIdx.x;
+#ifdef SDX_PROF
+  const int wave = tid >> 6;
+#endif
   // staged records: the LDS pool [0, nr_l), then (lane writers of heavy tiles) the spill region
   // [nr_l, nr); payload bytes likewise (StageRec.off with HEAP_SPILLED: spill region)
   constexpr int RMAX = T::PREC + (LM != 0 ? (int)SPILL_R : 0);
@@ -1465,10 +1492,12 @@ SDX_DEV void flush_tile(TileLds<NW, TM, LM>& L, const int* msg_of, int nvalid, c
       const uint32_t key = ((uint32_t)sr.proto << 16) | sr.rank;
       const uint32_t b0 = L.mbase[sr.msg], b1 = b0 + cntm[sr.msg];
       uint32_t rk = 0;
+      PROF_T(t_rk);
       for (uint32_t i = b0; i < b1; ++i) {
         const StageRec o = rec_at(bidx[i]);
         rk += (((uint32_t)o.proto << 16) | o.rank) < key ? 1u : 0u;
       }
+      PROF_ADDD(28, t_rk);
       sdx_result o;
       o.payload_off = L.heap_base + ((sr.off & HEAP_SPILLED) ? nh_l16 + (sr.off & ~HEAP_SPILLED) : sr.off);
       o.payload_len = sr.len;
@@ -1593,7 +1622,7 @@ SDX_DEV void pulses_tile(const void* __restrict__ bank, const sdx_pulse_batch& b
     for (int i = tid; i < nd; i += blockDim.x) L.msdesc[i] = ms_desc(bv.ms + i);
   }
 #ifdef SDX_PROF
-  if (lane < 28) L.prof[wave][lane] = 0;
+  if (lane < 29) L.prof[wave][lane] = 0;
 #endif
   __syncthreads();
   PROF_T(t_kernel);
@@ -2324,7 +2353,7 @@ SDX_DEV void pulses_tile(const void* __restrict__ bank, const sdx_pulse_batch& b
   if (tid == 0 && blk < 65536) g_wgt[2 * blk + 1] = __builtin_amdgcn_s_memrealtime();
 #endif
 #ifdef SDX_PROF
-  if (lane < 28) atomicAdd(&g_prof[lane], (unsigned long long)L.prof[wave][lane]);
+  if (lane < 29) atomicAdd(&g_prof[lane < 27 ? lane : lane + 5], (unsigned long long)L.prof[wave][lane]);
 #endif
 }
 
