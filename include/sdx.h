@@ -597,6 +597,42 @@ int sdx_route_records(const sdx_bank* bank, const sdx_route_table* table, const 
 int sdx_route_skip(const sdx_json_in* kinds, int k, int32_t n, const int16_t* route_dev, const uint8_t* repeat_dev,
                    int drop_unrouted, uint8_t* skip_dev, void* hip_stream);
 
+/* ---- receiver profiles -------------------------------------------------------------
+ * A stream of lines merges several receivers (source_dev, as sdx_mark_repeats_by_source takes it).  A
+ * PROFILE enables a set of protocol classes per kind (FHEM's whitelist_IDs / blacklist_IDs / developId, and
+ * rfmode for MN), a PROFILE TABLE maps every source id to one of up to 64 profiles; the blob's layout and
+ * its validator: csrc/sdx_profile_layout.h (pysignalduino_amd/profiles.py compiles it).
+ * sdx_profile_table_create validates the WHOLE blob on the host before anything is uploaded: a bad blob
+ * gives SDX_EINVAL and no device call; the kernels test no table contents.
+ * sdx_filter_records rewrites the launch outputs of kinds[0..k) (k = 1..4, no kind twice; of each only kind,
+ * desc_dev, rec_dev, cursor_dev and n = the chunk's n are read) into desc_out[i] [n], rec_out[i]
+ * [rec_cap[i]], cursor_out[i] [4] -- host arrays of k entries, buffers distinct from the inputs.  For line g
+ * of source s (0 when source_dev is NULL) with the mask E of kind i of profile of_source[s]:
+ *   status SDX_ST_OK: kept = the records r of [rec_begin, rec_begin + n_rec) with proto(r) in E, in order;
+ *     desc_out[i][g] = {begin', |kept|, SDX_ST_OK, 0}, rec_out[i][begin' + j] = the j-th kept record, all 16
+ *     bytes; begin' = the records kept by the lines g' < g: LINE order, dense, the same bytes every run;
+ *   any other status: the descriptor's 8 bytes, no records;
+ *   cursor_out[i] = the input cursor's four words with word 0 = the kept total.
+ * A proto not below the kind's class count is not enabled; a source id outside [0, n_sources) keeps nothing.
+ * A line whose range [begin', begin' + |kept|) does not fit rec_cap[i] gets {begin', 0, SDX_ST_OVF_OUT, 0} and
+ * stores nothing; bit 0 of cursor_out[i][2] is set and word 0 still carries the demand.  Nothing in
+ * rec_out[i] at or beyond min(total, rec_cap[i]) is written; every desc_out[i][0, n) and cursor word is.
+ * scratch_dev: sdx_profile_scratch_bytes(k, n) bytes, 16-byte aligned, contents free.  Three launches for
+ * all kinds together (count, scan, write; n = 0: the scan alone); no allocation, no synchronisation, no
+ * spinning, no global atomics.  SDX_EINVAL (nothing launched): a null bank, table, output array or entry,
+ * a table whose class counts are not the bank's, k outside 1..4, n < 0, bad kinds, a misaligned source_dev
+ * (4 bytes), scratch_dev (16), descriptor / cursor output (4) or record array (16). */
+typedef struct sdx_profile_table sdx_profile_table;
+int sdx_profile_table_create(const void* blob, size_t nbytes, int device, sdx_profile_table** out);
+int sdx_profile_table_destroy(sdx_profile_table* table);
+/* the host validator alone (no device call): NULL = a good blob, otherwise why it is refused (static text) */
+const char* sdx_profile_check(const void* blob, size_t nbytes);
+size_t sdx_profile_scratch_bytes(int k, int32_t n);
+int sdx_filter_records(const sdx_bank* bank, const sdx_profile_table* table, const sdx_json_in* kinds, int k,
+                       int32_t n, const int32_t* source_dev, sdx_desc* const* desc_out,
+                       sdx_result* const* rec_out, const uint32_t* rec_cap, uint32_t* const* cursor_out,
+                       void* scratch_dev, void* hip_stream);
+
 /* ---- unit-level entry ------------------------------------------------------------------------
  * The reference's helper methods that its own unit tests call on SDProtocols, evaluated on n
  * independent inputs in one launch (lane = item), with the device code the demodulation kernels

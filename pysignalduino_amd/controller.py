@@ -66,9 +66,14 @@ class BatchingParserTask:
                  logger: Optional[logging.Logger] = None, stream: bool = True, lag: int = 3,
                  collapse_repeats: bool = False, repeat_window: Optional[float] = None,
                  clock: Optional[Callable[[], int]] = None, routes=None, drop_unrouted: bool = False,
-                 route_topics: bool = False, route_match: str = "first"):
+                 route_topics: bool = False, route_match: str = "first", profiles=None):
         if publish not in ("objects", "json"):
             raise ValueError("publish must be 'objects' or 'json'")
+        # receiver profiles: a controller reads ONE receiver, so the table has one source
+        from .profiles import as_profiles
+        self.profiles = as_profiles(profiles)
+        if self.profiles is not None and self.profiles.n_sources != 1:
+            raise ValueError("a controller reads one receiver: profiles with one source (a Profile)")
         # payload routes: the texts' routes come from the device, so they need publish='json'
         from .routes import as_table
         self.routes = as_table(routes)
@@ -183,12 +188,16 @@ class BatchingParserTask:
         return f"{base}/state/messages"
 
     def _route_kw(self) -> dict:
+        kw = {} if self.profiles is None else {"profiles": self.profiles}   # without profiles the calls are as before
         if self.routes is None:
-            return {}
-        kw = {"routes": self.routes, "drop_unrouted": self.drop_unrouted}
+            return kw
+        kw.update(routes=self.routes, drop_unrouted=self.drop_unrouted)
         if self.route_match != "first":   # "first" calls exactly as before
             kw["route_match"] = self.route_match
         return kw
+
+    def _profile_kw(self) -> dict:
+        return {} if self.profiles is None else {"profiles": self.profiles}
 
     @staticmethod
     def _routed_items(r) -> List[Any]:
@@ -356,11 +365,11 @@ class BatchingParserTask:
             return out
         if times is not None:
             from .repeats import collapse_objects
-            results = p.parse_lines(lines)
+            results = p.parse_lines(lines, **self._profile_kw())
             collapse_objects(results, times, self.window_us, self._carry)
             return results
         from .repeats import objects_key
-        results = p.parse_lines(lines, collapse_repeats=True)
+        results = p.parse_lines(lines, collapse_repeats=True, **self._profile_kw())
         first = True
         for i, res in enumerate(results):
             k = objects_key(res)
@@ -376,6 +385,10 @@ class BatchingParserTask:
         kw = self._route_kw()
         return self.c.parser.parse_lines_routed(lines, kw.pop("routes"), **kw)
 
+    def _parse_profiled(self, lines: List[Any]) -> List[Any]:
+        p = self.c.parser
+        return (p.parse_lines_json if self.publish == "json" else p.parse_lines)(lines, **self._profile_kw())
+
     async def run(self) -> None:
         c = self.c
         if self.use_stream:
@@ -387,6 +400,7 @@ class BatchingParserTask:
                 if lines:
                     parse = (self._parse_collapsed if self.collapse else
                              self._parse_routed if self.routes is not None else
+                             self._parse_profiled if self.profiles is not None else
                              c.parser.parse_lines_json if self.publish == "json" else c.parser.parse_lines)
                     times = self._times_of(batch)
                     results = await asyncio.to_thread(parse, lines, *([] if times is None else [times]))

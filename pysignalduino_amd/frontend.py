@@ -332,18 +332,28 @@ class SignalParser:
         return check_times(times, n, sources=sources), w
 
     @staticmethod
-    def _source_args(collapse: bool, sources, n: int):
+    def _source_args(collapse: bool, sources, n: int, profiles=None):
         """-> the lines' source ids as int32[n], None without ``sources``; ValueError without
-        collapse_repeats and for ids that are no integers inside [0, 4096) (repeats.py)."""
+        collapse_repeats or ``profiles`` and for ids that are no integers inside [0, 4096) (repeats.py) --
+        with ``profiles`` (a profiles.ReceiverProfiles) inside its table's [0, S), and for a table of several
+        sources without ids."""
         if sources is None:
+            if profiles is not None and profiles.n_sources > 1:
+                raise ValueError(f"profiles for {profiles.n_sources} sources need the lines' source ids (sources=)")
             return None
-        if not collapse:
-            raise ValueError("sources needs collapse_repeats=True")
+        if not collapse and profiles is None:
+            raise ValueError("sources needs collapse_repeats=True or profiles")
         from .repeats import check_sources
-        return check_sources(sources, n)
+        return check_sources(sources, n, None if profiles is None else profiles.n_sources)
+
+    def _mn_elig(self, profiles=None) -> int:
+        """sdx_mn_batch.elig: the parser's rfmode, and with ``profiles`` only what some profile enables."""
+        elig = self.protocols.mn_eligibility(self.rfmode)
+        return elig if profiles is None else elig & profiles.mn_elig(self.protocols._bank)
 
     def parse_lines(self, lines: Sequence[Union[str, bytes]], collapse_repeats: bool = False, times=None,
-                    repeat_window: Optional[float] = None, sources=None) -> List[Union[List[DecodedMessage], Exception]]:
+                    repeat_window: Optional[float] = None, sources=None,
+                    profiles=None) -> List[Union[List[DecodedMessage], Exception]]:
         """Batch form of parse_line: one upload, one parse launch, one launch per demodulation
         variant, one read-back.  Returns one DecodedMessage list per line (or the ContractError
         for a line outside the device contract).  ``collapse_repeats``: a line that repeats the
@@ -352,14 +362,20 @@ class SignalParser:
         integer microseconds per line, non-decreasing): a run also ends once its last published line
         is more than the window old, as FHEM dispatches (repeats.py).  ``sources`` (one integer id per
         line, the receiver it came from): every source's lines are a stream of their own -- runs, keys and
-        the window's anchor per source, the times non-decreasing within a source."""
-        sources = self._source_args(collapse_repeats, sources, len(lines))
+        the window's anchor per source, the times non-decreasing within a source.  ``profiles`` (a
+        profiles.ReceiverProfiles, a Profile or a list of them): every line keeps only the messages
+        whose protocol its source's profile enables (``sources``: the ids, also without collapse_repeats; a table
+        of one source needs none) -- filtered on the device (sdx_filter_records) before anything is read back."""
+        from .profiles import as_profiles
+        profiles = as_profiles(profiles)
+        sources = self._source_args(collapse_repeats, sources, len(lines), profiles)
         times, w = self._window_args(collapse_repeats, times, repeat_window, len(lines), sources)
         if len(lines) == 0:
             return self._collapsed([], collapse_repeats)
         data, offsets, bad = pack_lines(lines)
         return self._collapsed(self._objects(lines, LineBatch(self.protocols._ensure(), data, offsets), offsets, bad,
-                                             len(data)), collapse_repeats, times, w, sources)
+                                             len(data), profiles, sources), collapse_repeats, times, w,
+                               sources if collapse_repeats else None)
 
     def _collapsed(self, out: list, collapse: bool, times=None, window_us=None, sources=None) -> list:
         """Object output: every payload is on the host already, so the repeats are marked there."""
@@ -368,9 +384,10 @@ class SignalParser:
             self.last_repeat_mask = collapse_objects(out, times, window_us, sources=sources)
         return out
 
-    def _objects(self, lines, lb: LineBatch, offsets: np.ndarray, bad: dict, nbytes: int):
+    def _objects(self, lines, lb: LineBatch, offsets: np.ndarray, bad: dict, nbytes: int, profiles=None, sources=None):
         """parse_lines from the uploaded batch on: ``lines`` indexable (lines[i] = line i's text),
-        ``offsets`` the host copy of lb.offsets, ``nbytes`` = offsets[n]."""
+        ``offsets`` the host copy of lb.offsets, ``nbytes`` = offsets[n].  ``profiles`` / ``sources``: the
+        launches' results go through sdx_filter_records before the objects are built from them."""
         n = len(lines)
         eng = self.protocols._ensure()
         bk = self.protocols._bank
@@ -391,8 +408,10 @@ class SignalParser:
             # result space: <= (MN protocols) records of <= (preamble + frame) bytes per line
             nmn = int(cnt[runtime.SEL_MN])
             res["MN"] = eng.run(runtime.KIND_MN, lb.mn_batch(), sel_short=sels[runtime.SEL_MN],
-                                mn_elig=self.protocols.mn_eligibility(self.rfmode),
+                                mn_elig=self._mn_elig(profiles),
                                 rec_cap=len(bk.mn_pids) * nmn + 1024, heap_cap=int(4 * nbytes + 64 * nmn + 65536))
+        if profiles is not None and res:
+            res = eng.filter_fetched(profiles, res, n, sources)
         # read-back of the per-line fields the Python objects need
         kind = lb.kind[:n].cpu().numpy()
         status = lb.status[:n].cpu().numpy()
@@ -442,8 +461,11 @@ class SignalParser:
             if st == runtime.LS_GENERAL:
                 gname, j = gen_of[i]
                 _, gdesc, grec, gheap, gvals, gcps = gen[gname]
-                out.append(self._general_messages(lines[i], i, plen, offsets, slot, meta, gname, gdesc[j], grec,
-                                                  gheap.tobytes(), abs(float(gvals[j, max(0, int(gcps[j]))]))))
+                g = self._general_messages(lines[i], i, plen, offsets, slot, meta, gname, gdesc[j], grec,
+                                           gheap.tobytes(), abs(float(gvals[j, max(0, int(gcps[j]))])))
+                if profiles is not None and isinstance(g, list):   # the general path's lists are built on the host
+                    g = profiles.filter(bk, 0 if sources is None else int(sources[i]), gname, g)
+                out.append(g)
                 continue
             if st != runtime.LS_OK or name not in res:
                 out.append([])
@@ -556,7 +578,7 @@ class SignalParser:
     def stream(self, chunk_lines: int = 250_000, chunk_bytes: Optional[int] = None, output: str = "json",
                lag: int = 3, collapse_repeats: bool = False, repeat_window: Optional[float] = None,
                repeat_sources: Optional[int] = None, routes=None, drop_unrouted: bool = False,
-               route_match: str = "first"):
+               route_match: str = "first", profiles=None):
         """A pipelined LineStream over this parser (pysignalduino_amd/stream.py): chunks of raw lines
         in, the controller's JSON texts (or the wire form) out, the PCIe copies, parse, demodulation
         and serialisation of successive chunks overlapping; the same per-line results as
@@ -565,7 +587,8 @@ class SignalParser:
         (a routes.RouteTable or a list of (name, pattern) pairs) / ``drop_unrouted``: payload routes, as
         parse_lines_routed: ChunkResult.route and items_routed(); None leaves the stream as it is.
         ``route_match="any"`` (with ``routes``): the line's first message that a route wants is the published
-        one; ChunkResult.pick holds its index."""
+        one; ChunkResult.pick holds its index.  ``profiles``: receiver profiles, every
+        submit names its lines' source ids as with ``repeat_sources`` (stream.py)."""
         from .stream import LineStream
         kw = {} if repeat_window is None else {"repeat_window": repeat_window}
         if repeat_sources is not None:
@@ -577,11 +600,14 @@ class SignalParser:
                 kw["route_match"] = route_match
         elif drop_unrouted:
             raise ValueError("drop_unrouted needs routes")
+        if profiles is not None:
+            kw["profiles"] = profiles
         return LineStream(self, chunk_lines=chunk_lines, chunk_bytes=chunk_bytes, output=output, lag=lag,
                           collapse_repeats=collapse_repeats, **kw)
 
     def parse_lines_json(self, lines: Sequence[Union[str, bytes]], collapse_repeats: bool = False, times=None,
-                         repeat_window: Optional[float] = None, sources=None) -> List[Union[Optional[str], Exception]]:
+                         repeat_window: Optional[float] = None, sources=None,
+                         profiles=None) -> List[Union[Optional[str], Exception]]:
         """Per line, the MQTT message text the reference controller publishes for it:
         ``MqttPublisher._message_to_json(parse_line(line)[0])`` (signalduino/controller.py:254-257,
         mqtt.py:227-245), or None when the line decodes to nothing -- parse, demodulation and JSON
@@ -593,8 +619,11 @@ class SignalParser:
         ends once its last published line is more than the window old (sdx_mark_repeats_timed).
         ``sources`` (one integer id per line, the receiver it came from; S = the largest id + 1): every
         source's lines are a stream of their own (sdx_mark_repeats_by_source), the times non-decreasing
-        within a source."""
-        sources = self._source_args(collapse_repeats, sources, len(lines))
+        within a source.  ``profiles`` (with ``sources``, also without collapse_repeats): receiver profiles as
+        parse_lines takes them -- the published message is the first one the line's source enables."""
+        from .profiles import as_profiles
+        profiles = as_profiles(profiles)
+        sources = self._source_args(collapse_repeats, sources, len(lines), profiles)
         times, w = self._window_args(collapse_repeats, times, repeat_window, len(lines), sources)
         if len(lines) == 0:
             if collapse_repeats:
@@ -602,11 +631,12 @@ class SignalParser:
             return []
         data, offsets, bad = pack_lines(lines)
         return self._texts(lines, LineBatch(self.protocols._ensure(), data, offsets), bad, len(data), collapse_repeats,
-                           times, w, sources)
+                           times, w, sources, profiles=profiles)
 
     def parse_lines_routed(self, lines: Sequence[Union[str, bytes]], routes, drop_unrouted: bool = False,
                            collapse_repeats: bool = False, times=None, repeat_window: Optional[float] = None,
-                           sources=None, route_match: str = "first") -> List[Union[None, Tuple[int, str], Exception]]:
+                           sources=None, route_match: str = "first",
+                           profiles=None) -> List[Union[None, Tuple[int, str], Exception]]:
         """parse_lines_json with payload routes: per line None, or (route_index, text) -- the
         text parse_lines_json gives, and the index of the first route of ``routes`` (a routes.RouteTable or
         a list of (name, pattern) pairs) whose pattern matches the payload of ``decoded[0]`` by ``re.search``,
@@ -619,14 +649,17 @@ class SignalParser:
         the published message is the first one, in the reference's list order, that some route matches
         (``decoded[0]`` when none does): its text, its repeat key and its route, matched on the device over
         every record of the line (sdx_route_records).  ``last_picks`` (uint16) holds that message's index;
-        "first" leaves it None."""
+        "first" leaves it None.  ``profiles``: as parse_lines_json; the routes see the filtered lists, and
+        ``last_picks`` indexes them."""
+        from .profiles import as_profiles
         from .routes import as_table
         _check_route_match(route_match, routes)
         table = as_table(routes)
         if table is None:
             raise ValueError("parse_lines_routed needs a route table")
         any_ = route_match == "any"
-        sources = self._source_args(collapse_repeats, sources, len(lines))
+        profiles = as_profiles(profiles)
+        sources = self._source_args(collapse_repeats, sources, len(lines), profiles)
         times, w = self._window_args(collapse_repeats, times, repeat_window, len(lines), sources)
         if len(lines) == 0:
             if collapse_repeats:
@@ -636,14 +669,15 @@ class SignalParser:
             return []
         data, offsets, bad = pack_lines(lines)
         return self._texts(lines, LineBatch(self.protocols._ensure(), data, offsets), bad, len(data), collapse_repeats,
-                           times, w, sources, routes=table, drop_unrouted=drop_unrouted, match_any=any_)
+                           times, w, sources, routes=table, drop_unrouted=drop_unrouted, match_any=any_, profiles=profiles)
 
     def _texts(self, lines, lb: LineBatch, bad: dict, nbytes: int, collapse: bool = False, times=None,
                window_us: Optional[int] = None, sources=None, routes=None, drop_unrouted: bool = False,
-               match_any: bool = False):
+               match_any: bool = False, profiles=None):
         """parse_lines_json from the uploaded batch on (``lines`` and ``nbytes`` as in _objects).  ``routes``
         (a routes.RouteTable; parse_lines_routed): every text becomes (route, text), see there; ``match_any``:
-        its route_match="any"."""
+        its route_match="any".  ``profiles`` (a profiles.ReceiverProfiles; ``sources``: the ids, or None for its
+        source 0): every kind's launch output goes through sdx_filter_records before anything else reads it."""
         n = len(lines)
         eng = self.protocols._ensure()
         bk = self.protocols._bank
@@ -668,7 +702,8 @@ class SignalParser:
             k = int(cnt[runtime.SEL_MN])
             jobs.append((runtime.KIND_MN, len(bk.mn_pids) * k + 1024, int(4 * nbytes + 64 * k + 65536),
                          int(6 * nbytes + 400 * k + 65536), [(lb.mn_batch(), sels[runtime.SEL_MN], False)]))
-        elig = self.protocols.mn_eligibility(self.rfmode)
+        elig = self._mn_elig(profiles)
+        rsources = sources if collapse else None   # the repeat pass's ids: without collapse the ids are the profiles' alone
         texts: List[Any] = [None] * n
         host_rows: List[int] = []   # lines whose text is built from parse_lines' objects (general paths)
 
@@ -730,7 +765,7 @@ class SignalParser:
             from .repeats import RepeatPass, apply_mask, count_sources, objects_key, text_key
             rpass = RepeatPass(eng, window_us, None if sources is None else count_sources(sources))
             rbufs = None
-        if collapse or routes is not None:
+        if collapse or routes is not None or profiles is not None:
             # every kind's launch first (their outputs stay on the device), then ONE sdx_mark_repeats over
             # them, then the serialiser with the mask: a repeat is never turned into text
             kept = []
@@ -752,6 +787,14 @@ class SignalParser:
                 else:
                     raise RuntimeError("result capacity overflow persists")
                 kept.append((kind, out, json_cap))
+            if kept and profiles is not None:
+                # right behind the launches: every line keeps the records its source's profile enables, compacted
+                # in line order; everything below reads the filtered outputs (they share the launches' heaps)
+                pbufs = eng.alloc_profiles(n, [out for _, out, _ in kept])
+                d_src = None if sources is None else eng.torch.from_numpy(np.ascontiguousarray(sources, np.int32)).to(eng.dev)
+                fouts = eng.filter_records(profiles, [eng.json_in(kind, out, lo, n) for kind, out, _ in kept], n, pbufs,
+                                           source=d_src)
+                kept = [(kind, fo, json_cap) for (kind, _, json_cap), fo in zip(kept, fouts)]
             if kept:   # a fresh stream of lines per call; nothing is read back but the mask (and the sources' table)
                 ins = [eng.json_in(kind, out, lo, n) for kind, out, _ in kept]
                 skip = None
@@ -764,7 +807,7 @@ class SignalParser:
                     kept = [(kind, dict(out, desc=v), json_cap) for (kind, out, json_cap), v in zip(kept, rb["views"])]
                 if collapse:
                     rbufs = rpass.alloc(n, pinned=False)
-                    rpass.enqueue(rbufs, ins, n, times=times, sources=sources)
+                    rpass.enqueue(rbufs, ins, n, times=times, sources=rsources)
                     skip = rbufs.mask
                 if match_any:
                     if rb["skip"] is not None:   # as below: with collapse the unrouted texts still come back
@@ -821,7 +864,9 @@ class SignalParser:
         has_text = np.fromiter((x is not None for x in texts), bool, n) if collapse else None
         host_keys = {}   # collapse: the host-resolved rows' keys (None: no result)
         if grows:  # general-path lines (rare): their objects through parse_lines, the text as _message_to_json
-            for i, g in zip(grows, self.parse_lines([lines[i] for i in grows])):
+            gkw = {} if profiles is None else {"profiles": profiles,
+                                               "sources": None if sources is None else [int(sources[i]) for i in grows]}
+            for i, g in zip(grows, self.parse_lines([lines[i] for i in grows], **gkw)):
                 if match_any and isinstance(g, list) and g:   # the published message is the picked one
                     pick[i], route[i], _ = routes.pick([m.payload for m in g])
                     g = g[int(pick[i]): int(pick[i]) + 1]
@@ -848,9 +893,10 @@ class SignalParser:
             fetched = {}
 
             def one_text(i):    # the line's published text on its own (match_any: the picked message's)
+                pkw = {} if profiles is None else {"profiles": profiles, "sources": None if sources is None else [int(sources[i])]}
                 if not match_any:
-                    return self.parse_lines_json([lines[i]])[0]
-                x = self.parse_lines_routed([lines[i]], routes, route_match="any")[0]
+                    return self.parse_lines_json([lines[i]], **pkw)[0]
+                x = self.parse_lines_routed([lines[i]], routes, route_match="any", **pkw)[0]
                 return x[1] if isinstance(x, tuple) else x
 
             def fetch_key(i):   # a flagged line whose run head the host does not know: the batch API
@@ -859,7 +905,7 @@ class SignalParser:
 
             dev_key_of = lambda i: text_key(_KIND_NAME[int(kinds[i])], texts[i])   # noqa: E731
             mask = rpass.exact_mask(rbufs, rep, has_text, dev_key_of, host_keys, fetch=fetch_key, times=times,
-                                    sources=sources)
+                                    sources=rsources)
 
             def drop(i):         # a host-resolved repeat, or a repeat of a host-resolved line
                 texts[i] = None
@@ -877,25 +923,32 @@ class SignalParser:
         return texts
 
     # -- byte-stream input ---------------------------------------------------------------------------
-    def parse_bytes(self, data, final: bool = True, collapse_repeats: bool = False):
+    def parse_bytes(self, data, final: bool = True, collapse_repeats: bool = False, profiles=None):
         """parse_lines over a transport's raw read buffer (bytes-like): the bytes are uploaded and split
         into lines on the device (sdx_split_lines: every '\\n' ends a line, as StreamReader.readline(),
         signalduino/transport.py:113-123).  ``final=True``: bytes after the last '\\n' are the last line
         (readline() at EOF); returns parse_lines' list for those lines.  ``final=False``: returns
         (that list for the terminated lines, the unterminated tail as bytes) -- prepend the tail to the
         next buffer.  There is no ``repeat_window`` here or in parse_bytes_json: one call has no per-line
-        arrival times (LineStream.submit_bytes takes one per read buffer)."""
+        arrival times (LineStream.submit_bytes takes one per read buffer).  ``profiles``: receiver profiles as
+        parse_lines takes them, for the one receiver the buffer was read from (a table of one source)."""
+        from .profiles import as_profiles
+        profiles = as_profiles(profiles)
+        self._source_args(collapse_repeats, None, 0, profiles)
         lines, lb, tail = self._split_bytes(data, final)
-        out = self._objects(lines, lb, lines.offsets, {}, int(lines.offsets[-1])) if len(lines) else []
+        out = self._objects(lines, lb, lines.offsets, {}, int(lines.offsets[-1]), profiles) if len(lines) else []
         out = self._collapsed(out, collapse_repeats)
         return out if final else (out, tail)
 
-    def parse_bytes_json(self, data, final: bool = True, collapse_repeats: bool = False):
+    def parse_bytes_json(self, data, final: bool = True, collapse_repeats: bool = False, profiles=None):
         """parse_lines_json over a raw read buffer (see parse_bytes; the same return forms)."""
+        from .profiles import as_profiles
+        profiles = as_profiles(profiles)
+        self._source_args(collapse_repeats, None, 0, profiles)
         lines, lb, tail = self._split_bytes(data, final)
         if collapse_repeats:
             self.last_repeat_mask = np.zeros(0, np.uint8)
-        out = self._texts(lines, lb, {}, int(lines.offsets[-1]), collapse_repeats) if len(lines) else []
+        out = self._texts(lines, lb, {}, int(lines.offsets[-1]), collapse_repeats, profiles=profiles) if len(lines) else []
         return out if final else (out, tail)
 
     def _split_bytes(self, data, final: bool):

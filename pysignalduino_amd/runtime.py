@@ -51,7 +51,9 @@ EXPORTED = ["sdx_abi_version", "sdx_last_error", "sdx_source_hash", "sdx_layout_
             "sdx_repeat_scratch_bytes", "sdx_repeat_tile", "sdx_mark_repeats_timed", "sdx_repeat_timed_state_bytes",
             "sdx_repeat_timed_scratch_bytes", "sdx_mark_repeats_by_source", "sdx_repeat_sources_state_bytes",
             "sdx_repeat_sources_scratch_bytes", "sdx_route_table_create", "sdx_route_table_destroy",
-            "sdx_route_table_lds_routes", "sdx_route_lines", "sdx_route_records", "sdx_route_skip"]
+            "sdx_route_table_lds_routes", "sdx_route_lines", "sdx_route_records", "sdx_route_skip",
+            "sdx_profile_table_create", "sdx_profile_table_destroy", "sdx_profile_check", "sdx_profile_scratch_bytes",
+            "sdx_filter_records"]
 REPEAT_SOURCES_MAX = 4096   # SDX_REPEAT_SOURCES_MAX
 # sdx_repeat_source_entry (csrc/sdx_repeat_layout.h): a source's slot header after a chunk + its last result-bearing line
 REPEAT_SOURCE_ENTRY = np.dtype([("valid", "<u4"), ("kind", "<u4"), ("proto", "<u4"), ("len", "<u4"), ("t", "<i8"),
@@ -290,6 +292,17 @@ def load_library(path: Optional[str] = None):
     lib.sdx_route_records.restype = c_int
     lib.sdx_route_skip.argtypes = [POINTER(SdxJsonIn), c_int, c_int32, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
     lib.sdx_route_skip.restype = c_int
+    lib.sdx_profile_table_create.argtypes = [c_void_p, c_size_t, c_int, POINTER(c_void_p)]
+    lib.sdx_profile_table_create.restype = c_int
+    lib.sdx_profile_table_destroy.argtypes = [c_void_p]
+    lib.sdx_profile_table_destroy.restype = c_int
+    lib.sdx_profile_check.argtypes = [c_void_p, c_size_t]
+    lib.sdx_profile_check.restype = ctypes.c_char_p
+    lib.sdx_profile_scratch_bytes.argtypes = [c_int, c_int32]
+    lib.sdx_profile_scratch_bytes.restype = c_size_t
+    lib.sdx_filter_records.argtypes = [c_void_p, c_void_p, POINTER(SdxJsonIn), c_int, c_int32, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.sdx_filter_records.restype = c_int
     lib.sdx_parse_lines.argtypes = [POINTER(SdxLines), POINTER(SdxLinesOut), c_void_p]
     lib.sdx_parse_lines.restype = c_int
     lib.sdx_select_lines.argtypes = [POINTER(SdxLinesOut), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
@@ -412,6 +425,41 @@ class DeviceRouteTable:
             self.close()
         except Exception:
             pass
+
+
+class DeviceProfileTable:
+    """A receiver-profile table on the device (sdx_profile_table_create): ``handle``, ``profiles`` (the
+    profiles.ReceiverProfiles).  A blob the host validator refuses raises RuntimeError and uploads nothing."""
+
+    def __init__(self, eng: "Engine", rp, blob: Optional[bytes] = None):
+        self.lib, self.profiles = eng.lib, rp
+        blob = rp.blob(eng.bank) if blob is None else blob
+        h = c_void_p()
+        buf = ctypes.create_string_buffer(blob, len(blob))
+        with eng.torch.cuda.device(eng.device):
+            _check(self.lib, self.lib.sdx_profile_table_create(ctypes.cast(buf, c_void_p), len(blob), eng.device,
+                                                               ctypes.byref(h)))
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None) is not None and self.handle.value:
+            self.lib.sdx_profile_table_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def profile_check(blob: bytes) -> Optional[str]:
+    """The host validator of a profile table's blob (sdx_profile_validate; no device): None = good, otherwise why
+    it is refused."""
+    lib = load_library()
+    buf = ctypes.create_string_buffer(blob, len(blob))
+    why = lib.sdx_profile_check(ctypes.cast(buf, c_void_p), len(blob))
+    return None if why is None else why.decode()
 
 
 class Engine:
@@ -923,6 +971,86 @@ class Engine:
         self._mark("route_skip", lambda bank, arr, k, n_, *a: self.lib.sdx_route_skip(arr, k, n_, *a),
                    json_ins, n, [(route, 2 * n), (skip, n), (repeat, n)],
                    (_ptr(route), _ptr(repeat), 1 if drop_unrouted else 0, _ptr(skip)), stream)
+
+    # -- receiver profiles (sdx_filter_records) -------------------------------------
+    def profile_table(self, rp) -> "DeviceProfileTable":
+        """``rp`` (profiles.ReceiverProfiles, a Profile or a list of them) compiled against this engine's bank,
+        validated and uploaded (sdx_profile_table_create); the handle is kept on the object, one per engine."""
+        from .profiles import as_profiles
+        rp = as_profiles(rp)
+        cache = rp.__dict__.setdefault("_device", {})
+        if id(self) not in cache or cache[id(self)][0] is not self:
+            cache[id(self)] = (self, DeviceProfileTable(self, rp))
+        return cache[id(self)][1]
+
+    def alloc_profiles(self, n: int, outs):
+        """The buffers of filter_records for chunks of up to n lines whose launches write ``outs`` (alloc_out's
+        dictionaries, one per kind): {"outs": one filtered out per kind -- "desc", "rec" and "cursor" of its own, the
+        launch's "heap" and capacities --, "scratch"}."""
+        t, d, n = self.torch, self.dev, max(int(n), 1)
+        f = []
+        for o in outs:
+            x = dict(o)
+            x.update(desc=t.empty(n * DESC_DT.itemsize, dtype=t.uint8, device=d),
+                     rec=t.empty(max(o["rec_cap"], 1) * RES_DT.itemsize, dtype=t.uint8, device=d),
+                     cursor=t.zeros(4, dtype=t.int32, device=d), work=None, wire=None, xrec=None)
+            f.append(x)
+        size = int(self.lib.sdx_profile_scratch_bytes(max(len(outs), 1), n))
+        return {"outs": f, "scratch": t.empty(size, dtype=t.uint8, device=d)}
+
+    def filter_records(self, table, json_ins, n: int, bufs, source=None, stream=None, rec_caps=None):
+        """sdx_filter_records on ``stream`` (default: the current one; no host sync): the launch outputs behind
+        ``json_ins`` (json_in, one per kind) with every line keeping only the records its source's profile enables,
+        compacted in line order into ``bufs`` (alloc_profiles').  ``source``: a device int32 tensor, one id per line;
+        None = every line is source 0.  ``rec_caps``: the record capacities to declare (default: the buffers').
+        Returns bufs["outs"]: filtered outs shaped like alloc_out's, sharing the launches' heaps."""
+        n = int(n)
+        if not isinstance(table, DeviceProfileTable):
+            table = self.profile_table(table)
+        outs = bufs["outs"]
+        if len(outs) != len(json_ins):
+            raise ValueError("filter_records: one output per kind")
+        k = max(len(outs), 1)
+        caps = [o["rec_cap"] for o in outs] if rec_caps is None else [int(c) for c in rec_caps]
+        for o, c in zip(outs, caps):
+            if o["rec"].numel() < c * RES_DT.itemsize:
+                raise ValueError("filter_records: a record buffer is smaller than its declared capacity")
+        darr = (c_void_p * k)(*[_ptr(o["desc"]) for o in outs])
+        rarr = (c_void_p * k)(*[_ptr(o["rec"]) for o in outs])
+        carr = (c_void_p * k)(*[_ptr(o["cursor"]) for o in outs])
+        caparr = (ctypes.c_uint32 * k)(*caps)
+        need = int(self.lib.sdx_profile_scratch_bytes(k, n)) if 1 <= len(outs) <= 4 and n >= 0 else 0
+        self._mark("filter_records",
+                   lambda bank, arr, k_, n_, *a: self.lib.sdx_filter_records(bank, table.handle, arr, k_, n_, *a),
+                   json_ins, n, [(source, 4 * n), (bufs["scratch"], need)] + [(o["desc"], 8 * n) for o in outs],
+                   (_ptr(source), darr, rarr, caparr, carr, _ptr(bufs["scratch"])), stream)
+        return outs
+
+    def filter_fetched(self, table, res: dict, n: int, sources=None) -> dict:
+        """filter_records for results already on the host (run()'s): ``res`` maps "MU" / "MS" / "MC" / "MN" to
+        (desc, rec, heap) as run() returns them; their descriptors and records go up again, through the pass, and
+        come back filtered (the heaps stay: payload offsets are unchanged).  ``sources``: int32[n] or None."""
+        t = self.torch
+        names = [k for k in ("MU", "MS", "MC", "MN") if k in res]
+        up = lambda a: t.from_numpy(np.frombuffer(a.tobytes(), np.uint8).copy()).to(self.dev)   # noqa: E731
+        outs, ins = [], []
+        for name in names:
+            desc, rec, _ = res[name]
+            o = {"desc": up(desc) if len(desc) else t.zeros(8, dtype=t.uint8, device=self.dev),
+                 "rec": up(rec) if len(rec) else t.zeros(RES_DT.itemsize, dtype=t.uint8, device=self.dev),
+                 "cursor": t.tensor([len(rec), 0, 0, 0], dtype=t.int32, device=self.dev), "rec_cap": len(rec), "heap_cap": 0, "n": n}
+            o["heap"] = o["desc"]    # never read by the pass
+            outs.append(o)
+            ins.append(self.json_in(("MU", "MS", "MC", "MN").index(name), o, {"meta": o["desc"]}, n))
+        bufs = self.alloc_profiles(n, outs)
+        src = None if sources is None else t.from_numpy(np.ascontiguousarray(sources, np.int32)).to(self.dev)
+        f = self.filter_records(table, ins, n, bufs, source=src)
+        out = dict(res)
+        for name, o in zip(names, f):
+            total = int(o["cursor"][0].item())
+            out[name] = (o["desc"][: n * DESC_DT.itemsize].cpu().numpy().view(DESC_DT).copy(),
+                         o["rec"][: total * RES_DT.itemsize].cpu().numpy().view(RES_DT).copy(), res[name][2])
+        return out
 
     def alloc_json(self, items: int, cap: int):
         t, d = self.torch, self.dev

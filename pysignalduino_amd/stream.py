@@ -291,6 +291,14 @@ class _Slot:
         if ls.collapse:   # the repeat pass's buffers: the mask, and the pinned copies the chunk's times / ids go through
             self.rb = ls.repeats.alloc(C, pinned=True)
             self.rep, self.h_times, self.h_src = self.rb.mask, self.rb.h_times, self.rb.h_src
+        if ls.profiles is not None:
+            # the profile pass's outputs: per kind descriptors, records and a cursor of their own beside the
+            # launch's (whose heap they share); the ids come up in the repeat pass's buffers, or in the slot's own
+            self.pf = eng.alloc_profiles(C, list(self.outs.values()))
+            self.fouts = dict(zip(self.outs, self.pf["outs"]))
+            if ls.n_sources is None and ls.profiles.n_sources > 1:
+                self.p_d_src = t.zeros(C, dtype=t.int32, device=eng.dev)
+                self.p_h_src = t.zeros(C, dtype=t.int32).pin_memory()
         if ls.routes is not None:   # the route pass's outputs; its skip mask only where the device drops the unrouted
             extra = {"pick": True, "views": len(self.outs)} if ls.match_any else {}   # "first": the call as it was
             self.rt = eng.alloc_routes(C, mask=False, skip=ls.device_drop, **extra)
@@ -338,9 +346,14 @@ class LineStream:
     def __init__(self, parser, chunk_lines: int = 250_000, chunk_bytes: Optional[int] = None, output: str = "json",
                  lag: int = 3, collapse_repeats: bool = False, repeat_window: Optional[float] = None,
                  repeat_sources: Optional[int] = None, routes=None, drop_unrouted: bool = False,
-                 route_match: str = "first"):
+                 route_match: str = "first", profiles=None):
         if output not in ("json", "wire"):
             raise ValueError("output must be 'json' or 'wire'")
+        from .profiles import as_profiles
+        self.profiles = as_profiles(profiles)   # receiver profiles; None: no pass, no buffer
+        if self.profiles is not None and output != "json":
+            # the exchange pack reads the demodulation kernels' own per-message counts, which the pass does not rewrite
+            raise ValueError("profiles need output='json'")
         from .frontend import _check_route_match
         _check_route_match(route_match, routes)
         self.match_any = route_match == "any"
@@ -358,6 +371,12 @@ class LineStream:
         self.n_sources = None if repeat_sources is None else runtime._n_sources(repeat_sources)
         if self.n_sources is not None and not self.collapse:
             raise ValueError("repeat_sources needs collapse_repeats=True")
+        if self.profiles is not None and self.n_sources is not None and self.profiles.n_sources != self.n_sources:
+            raise ValueError(f"the profile table maps {self.profiles.n_sources} sources, repeat_sources is {self.n_sources}")
+        # the ids a submit names: the repeat pass's, or (several receivers' profiles without it) the profile pass's alone
+        self.id_sources = self.n_sources
+        if self.id_sources is None and self.profiles is not None and self.profiles.n_sources > 1:
+            self.id_sources = self.profiles.n_sources
         self._last_times = {}     # repeat_sources with a window: source -> its last submitted line's time
         self._carries = {}        # repeat_sources, submit_bytes: source -> its unterminated tail
         import torch
@@ -378,6 +397,8 @@ class LineStream:
             self.rep_ev = None
         if self.routes is not None:
             self.dtable = self.eng.route_table(self.routes)
+        if self.profiles is not None:
+            self.ptable = self.eng.profile_table(self.profiles)
         # json: the device leaves unrouted lines out of the text buffer -- unless repeats are collapsed: the
         # host tracker then needs the key of every line that is no repeat, so those texts come back and are
         # dropped in _collect.  wire: the sections are unchanged, the route only travels beside them
@@ -399,6 +420,8 @@ class LineStream:
         self.done: Deque[ChunkResult] = collections.deque()
         self.next_id = 0
         self.elig = parser.protocols.mn_eligibility(parser.rfmode)
+        if self.profiles is not None:   # an MN protocol no profile enables is never run
+            self.elig &= self.profiles.mn_elig(self.bank)
         self.h2d_bytes = self.d2h_bytes = 0
         self.kernel_events = []   # (parse start, parse end, demod start, demod end) per chunk
         self._carry = bytearray()  # submit_bytes: the unterminated tail of the calls so far
@@ -407,19 +430,26 @@ class LineStream:
     def submit(self, lines: Sequence[Union[str, bytes]], times=None, sources=None) -> int:
         from .frontend import pack_lines
         sources = self._check_sources(sources, len(lines))   # before anything is packed or launched
-        times = self._check_times(times, len(lines), sources)
+        times = self._check_times(times, len(lines), self._rsrc(sources))
         data, offsets, bad = pack_lines(lines, copy=False)   # read once, into the slot's pinned buffer
         return self.submit_packed(data, offsets, lines=lines, bad=bad, times=times, sources=sources)
 
     def _check_sources(self, sources, n: int):
-        """A chunk's source ids as int32[n] (None on a stream without repeat_sources); ValueError when they
-        are missing, given to a stream without repeat_sources, or outside [0, S)."""
-        if self.n_sources is None:
-            if sources is not None:
+        """A chunk's source ids as int32[n] (None on a stream without repeat_sources or several receivers'
+        profiles); ValueError when they are missing, given to a stream that takes none, or outside [0, S)."""
+        if self.id_sources is None:
+            if sources is not None and self.profiles is None:
                 raise ValueError("sources given, but the stream has no repeat_sources")
+            if sources is not None:      # one receiver's profiles: every id must be 0, and none need be given
+                from .repeats import check_sources
+                check_sources(sources, n, 1)
             return None
         from .repeats import check_sources
-        return check_sources(sources, n, self.n_sources)
+        return check_sources(sources, n, self.id_sources)
+
+    def _rsrc(self, sources):
+        """The ids as the repeat pass sees them: None unless the stream has repeat_sources."""
+        return sources if self.n_sources is not None else None
 
     def _check_times(self, times, n: int, sources=None):
         """A chunk's arrival times as int64[n] (None without a window); ValueError when they are missing,
@@ -444,7 +474,7 @@ class LineStream:
             raise ValueError(f"chunk of {n} lines / {int(offsets[-1] - offsets[0])} bytes exceeds the stream's "
                              f"capacity ({self.C} lines, {self.B} bytes)")
         sources = self._check_sources(sources, n)
-        times = self._check_times(times, n, sources)
+        times = self._check_times(times, n, self._rsrc(sources))
         s = self._take_slot(n)
         self._set_times(s, times, sources)
         s.lines, s.bad = lines, bad or {}
@@ -469,13 +499,13 @@ class LineStream:
         s.times = s.sources = None
         if sources is not None:
             n = len(sources)
-            s.sources = s.h_src.numpy()[:n]
+            s.sources = (s.h_src if self.n_sources is not None else s.p_h_src).numpy()[:n]
             s.sources[:] = sources
         if times is not None:
             n = len(times)
             s.times = s.h_times.numpy()[:n]     # the slot's own copy: the caller's array may change
             s.times[:] = times
-            if n and sources is not None:       # every source's last line of the chunk
+            if n and self._rsrc(sources) is not None:       # every source's last line of the chunk
                 ids, back = np.unique(s.sources[::-1], return_index=True)
                 for sid, j in zip(ids.tolist(), (n - 1 - back).tolist()):
                     self._last_times[sid] = int(s.times[j])
@@ -488,7 +518,10 @@ class LineStream:
             runtime.copy_async(s.rb.d_times[: s.n], s.h_times[: s.n], self.cin)
             self.h2d_bytes += 8 * s.n
         if s.sources is not None and s.n:
-            runtime.copy_async(s.rb.d_src[: s.n], s.h_src[: s.n], self.cin)
+            if self.n_sources is not None:
+                runtime.copy_async(s.rb.d_src[: s.n], s.h_src[: s.n], self.cin)
+            else:
+                runtime.copy_async(s.p_d_src[: s.n], s.p_h_src[: s.n], self.cin)
             self.h2d_bytes += 4 * s.n
 
     def _queued(self, s: _Slot) -> int:
@@ -516,15 +549,18 @@ class LineStream:
         it queues has that id, the tail is carried to the next buffer of the SAME source, and ``time`` must
         not be earlier than that source's previous one."""
         t = self.torch
-        if self.n_sources is None:
-            if source is not None:
-                raise ValueError("source given, but the stream has no repeat_sources")
+        if self.id_sources is None:
+            if source is not None and (self.profiles is None or source != 0):
+                raise ValueError("source given, but the stream has no repeat_sources" if self.profiles is None else
+                                 "the stream's profile table has one source: source must be 0")
+            source = None
         else:
-            if source is None or int(source) != source or not 0 <= int(source) < self.n_sources:
-                raise ValueError(f"a stream with repeat_sources needs the read buffer's source id (source=) "
-                                 f"inside [0, {self.n_sources})")
+            if source is None or int(source) != source or not 0 <= int(source) < self.id_sources:
+                raise ValueError(f"a stream with repeat_sources or several receivers' profiles needs the read buffer's "
+                                 f"source id (source=) inside [0, {self.id_sources})")
             source = int(source)
-        last_time = self._last_time if source is None else self._last_times.get(source)
+        tsrc = self._rsrc(source)     # times run per source only where the repeat pass does
+        last_time = self._last_time if tsrc is None else self._last_times.get(tsrc)
         if self.window_us is None:
             if time is not None:
                 raise ValueError("time given, but the stream has no repeat_window")
@@ -536,10 +572,10 @@ class LineStream:
                     raise ValueError("time: integer microseconds")
                 if last_time is not None and int(time) < last_time:
                     raise ValueError("times must not decrease over a stream's lines")
-                if source is None:
+                if tsrc is None:
                     self._last_time = int(time)
                 else:
-                    self._last_times[source] = int(time)
+                    self._last_times[tsrc] = int(time)
         if isinstance(buf, (bytes, bytearray)):
             arr = np.frombuffer(buf, np.uint8)
             view = buf if len(buf) <= 2 * _NlView.PART else _NlView(arr)   # a read buffer: bytes' own rfind / count
@@ -566,7 +602,7 @@ class LineStream:
     def close_bytes(self, source: Optional[int] = None) -> List[int]:
         """End of the byte stream: a carried tail becomes the last line (submit_bytes(b"", final=True)).
         With ``repeat_sources``: every source's tail, in id order, or only that of ``source``."""
-        if self.n_sources is None:
+        if self.id_sources is None:
             return self.submit_bytes(b"", final=True, **({} if source is None else {"source": source}))
         ids = []
         for sid in (sorted(self._carries) if source is None else [source]):
@@ -582,7 +618,7 @@ class LineStream:
         s = self._take_slot(n)
         s.lines, s.bad = None, {}
         s.data = s.offsets = None
-        when = self._last_time if source is None else self._last_times.get(source)
+        when = self._last_time if self._rsrc(source) is None else self._last_times.get(source)
         self._set_times(s, None if self.window_us is None else np.full(n, when, np.int64),
                         None if source is None else np.full(n, source, np.int32))
         self._stage_a_bytes(s, np.frombuffer(bytes(carry), np.uint8), pinned_buf, arr, lo, hi, final)
@@ -774,10 +810,20 @@ class LineStream:
                         eng.launch_pulses(kd, pb, s.outs[name], sel=sels[long_], long_variant=True)
             s.cnt = cnt
             lo = {"meta": lb.meta, "pat_val": lb.pat_val, "cp_slot": lb.cp_slot}
+            outs = s.outs
+            if self.profiles is not None:
+                # right behind the launches: every line keeps the records its source's profile enables;
+                # everything below reads the filtered outputs.  The ids came up with the chunk's bytes (stage A)
+                ins = [eng.json_in(kd, s.outs[name], lo, n, 2) for name, kd, _, _ in _KINDS if name in s.outs]
+                for o in s.pf["outs"]:
+                    o["n"] = n
+                d_src = None if s.sources is None else s.rb.d_src if self.n_sources is not None else s.p_d_src
+                eng.filter_records(self.ptable, ins, n, s.pf, source=d_src, stream=sd)
+                outs = s.fouts
             if self.match_any:
                 # every line's published record and the views in which it owns exactly that one;
                 # nothing of this waits for the previous chunk
-                ins = [eng.json_in(kd, s.outs[name], lo, n, 2) for name, kd, _, _ in _KINDS if name in s.outs]
+                ins = [eng.json_in(kd, outs[name], lo, n, 2) for name, kd, _, _ in _KINDS if name in outs]
                 eng.route_records(self.dtable, ins, n, s.rt["route"], s.rt["pick"], s.rt["views"], stream=sd)
                 vins = [eng.json_in_view(ji, v) for ji, v in zip(ins, s.rt["views"])]
             if self.collapse:
@@ -785,21 +831,21 @@ class LineStream:
                 # demodulation stream); this chunk's demodulation above is already enqueued beside it
                 if self.rep_ev is not None:
                     sd.wait_event(self.rep_ev)
-                ins = vins if self.match_any else [eng.json_in(kd, s.outs[name], lo, n, 2)
-                                                   for name, kd, _, _ in _KINDS if name in s.outs]
+                ins = vins if self.match_any else [eng.json_in(kd, outs[name], lo, n, 2)
+                                                   for name, kd, _, _ in _KINDS if name in outs]
                 # the chunk's times and ids came up with its bytes (stage A, in front of the parse)
                 self.repeats.enqueue(s.rb, ins, n, sd)
                 self.rep_ev = t.cuda.Event()
                 self.rep_ev.record(sd)
             skip = {"skip": s.rep} if self.collapse else {}
-            jouts = s.outs
+            jouts = outs
             if self.match_any:   # the match came first; the serialiser reads the picked views
-                jouts = {name: dict(s.outs[name], desc=v) for name, v in zip(s.outs, s.rt["views"])}
+                jouts = {name: dict(outs[name], desc=v) for name, v in zip(outs, s.rt["views"])}
                 if s.rt["skip"] is not None:
                     eng.route_skip(vins, n, s.rt["route"], s.rt["skip"], drop_unrouted=True, stream=sd)
                     skip = {"skip": s.rt["skip"]}
             elif self.routes is not None:   # behind the repeat pass, in front of the serialiser
-                ins = [eng.json_in(kd, s.outs[name], lo, n, 2) for name, kd, _, _ in _KINDS if name in s.outs]
+                ins = [eng.json_in(kd, outs[name], lo, n, 2) for name, kd, _, _ in _KINDS if name in outs]
                 eng.route_lines(self.dtable, ins, n, s.rt["route"], None, s.rt["skip"], drop_unrouted=self.drop, stream=sd)
                 if s.rt["skip"] is not None:
                     skip = {"skip": s.rt["skip"]}
@@ -924,12 +970,13 @@ class LineStream:
             rows = sorted(rows)
             lines = [self._line(s, i) for i in rows]
             host_picks = None
+            pkw = self._profile_args(s, rows)
             if self.match_any and self.output == "json":   # the picked messages' texts, with their routes and picks
                 res = [x[1] if isinstance(x, tuple) else x
-                       for x in self.parser.parse_lines_routed(lines, self.routes, route_match="any")]
+                       for x in self.parser.parse_lines_routed(lines, self.routes, route_match="any", **pkw)]
                 host_picks = dict(zip(rows, zip(self.parser.last_picks.tolist(), self.parser.last_routes.tolist())))
             else:
-                res = (self.parser.parse_lines_json(lines) if self.output == "json" else self.parser.parse_lines(lines))
+                res = (self.parser.parse_lines_json(lines, **pkw) if self.output == "json" else self.parser.parse_lines(lines))
             for i, x in zip(rows, res):
                 r.host[i] = s.bad[i] if i in s.bad else x
         if self.routes is not None:   # the device's routes; a host-resolved line's from the same tables on the host
@@ -944,6 +991,8 @@ class LineStream:
             else:
                 for i, x in r.host.items():
                     r.route[i] = self._host_route(x)
+        if s.sources is not None:
+            r.source = s.sources.copy()
         if self.collapse:
             self._fix_repeats(s, r, ho[b + 2 * n: b + 3 * n], redo_kinds, kname)
         if self.drop and self.output == "json":   # published = result-bearing, no repeat, routed
@@ -956,6 +1005,13 @@ class LineStream:
         self.inflight.remove(s)
         s.reset()
         s.stage = 0
+
+    def _profile_args(self, s: _Slot, rows) -> dict:
+        """The batch API's profile arguments for the lines ``rows`` of a chunk: a host-resolved line is filtered by
+        the same table (profiles.ReceiverProfiles.filter and the one-shot calls' own pass)."""
+        if self.profiles is None:
+            return {}
+        return {"profiles": self.profiles, "sources": None if s.sources is None else [int(s.sources[i]) for i in rows]}
 
     def _host_route(self, x) -> int:
         """The route of a host-resolved line from its batch-API result (a text, or parse_lines' list)."""
@@ -979,9 +1035,10 @@ class LineStream:
         fetched = {}
 
         def one_text(i):       # the line's published text on its own (route_match="any": the picked message's)
+            pkw = self._profile_args(s, [i])
             if not self.match_any:
-                return self.parser.parse_lines_json([self._line(s, i)])[0]
-            x = self.parser.parse_lines_routed([self._line(s, i)], self.routes, route_match="any")[0]
+                return self.parser.parse_lines_json([self._line(s, i)], **pkw)[0]
+            x = self.parser.parse_lines_routed([self._line(s, i)], self.routes, route_match="any", **pkw)[0]
             return x[1] if isinstance(x, tuple) else x
 
         def fetch(i):
@@ -997,10 +1054,8 @@ class LineStream:
                 return text_key(name_of(i), bytes(blob[o: o + int(r.len[i])]).decode("ascii"))
         else:
             has_key, dev_key_of = self._wire_keys(r)
-        if s.sources is not None:
-            r.source = s.sources.copy()
         r.repeat = mask = self.repeats.exact_mask(s.rb, rep, has_key, dev_key_of, host_keys, redo, fetch,
-                                                  times=s.times, sources=r.source, bank=self.bank)
+                                                  times=s.times, sources=self._rsrc(r.source), bank=self.bank)
         if not js:
             return
 
