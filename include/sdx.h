@@ -633,6 +633,40 @@ int sdx_filter_records(const sdx_bank* bank, const sdx_profile_table* table, con
                        sdx_result* const* rec_out, const uint32_t* rec_cap, uint32_t* const* cursor_out,
                        void* scratch_dev, void* hip_stream);
 
+/* ---- dispatch rules ----------------------------------------------------------------
+ * FHEM dispatches every message of a line, stops after maxMuMsgRepeat messages of one protocol, and drops a
+ * message equal to the one just dispatched unless its protocol carries dispatchequals.  For one line's
+ * records r_0 .. r_{m-1} of one kind, in list order, with cap = max_repeat[kind] and K = keep_equal[kind]:
+ *   run = 0; prev_proto = none; last = none
+ *   for j in 0 .. m-1:
+ *     run = proto(r_j) == prev_proto ? run + 1 : 1;  prev_proto = proto(r_j)
+ *     if cap > 0 and run > cap:  r_j is dropped and does not become last
+ *     else: eq = last exists and proto(r_j) == proto(last) and payload(r_j) == payload(last) (length, then bytes)
+ *           last = r_j;  r_j is dropped when drop_equal and eq and proto(r_j) not in K, kept otherwise
+ * bit_length and msg are not part of the key; a proto at or above the kind's class count is in no mask.
+ * r_0 is always kept: a result-bearing line stays one, with the same first record.  The pass is idempotent.
+ * sdx_dispatch_rules is a plain host struct, copied into the kernel arguments: no device table, nothing to
+ * create or destroy.  csrc/sdx_dispatch_layout.h holds its validator (a mask bit at or above the bank's class
+ * count of that kind, a negative cap, a non-zero res are refused).
+ * sdx_dispatch_records rewrites the launch outputs of kinds[0..k) exactly as sdx_filter_records does (the same
+ * arguments, outputs, LINE-ordered dense records copied with all 16 bytes, cursor words, overflow contract and
+ * SDX_EINVAL cases; of each kind heap_dev is read too, the payloads stay in the launch's heap), with ``kept``
+ * = the records the definition keeps.  A payload comparison happens only after proto and length agree and reads
+ * nothing outside [payload_off, payload_off + payload_len) of either record.  scratch_dev:
+ * sdx_dispatch_scratch_bytes(k, n) bytes, 16-byte aligned, contents free.  Three launches for all kinds
+ * together (count, scan, write; n = 0: the scan alone); no allocation, no synchronisation, no spinning, no
+ * global atomics.  SDX_EINVAL (nothing launched) also for null rules, rules the validator refuses, a null heap. */
+typedef struct {
+  uint64_t keep_equal[4][4]; /* by enum sdx_kind: 256 bits, bit c = class c (sdx_result.proto) is never equal-dropped */
+  int32_t max_repeat[4];     /* by enum sdx_kind: records kept of one run of a protocol, 0 = no cap */
+  int32_t drop_equal;        /* 0 = the equal-message rule is off */
+  int32_t res;               /* 0 */
+} sdx_dispatch_rules;        /* 152 bytes */
+size_t sdx_dispatch_scratch_bytes(int k, int32_t n);
+int sdx_dispatch_records(const sdx_bank* bank, const sdx_dispatch_rules* rules, const sdx_json_in* kinds, int k,
+                         int32_t n, sdx_desc* const* desc_out, sdx_result* const* rec_out, const uint32_t* rec_cap,
+                         uint32_t* const* cursor_out, void* scratch_dev, void* hip_stream);
+
 /* ---- unit-level entry ------------------------------------------------------------------------
  * The reference's helper methods that its own unit tests call on SDProtocols, evaluated on n
  * independent inputs in one launch (lane = item), with the device code the demodulation kernels

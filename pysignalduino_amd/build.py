@@ -15,6 +15,7 @@ SRCS = [os.path.join(HERE, "csrc", "sdx_kernels.hip"),   # demodulation kernels 
         os.path.join(HERE, "csrc", "sdx_repeat.hip"),    # repeat suppression (sdx_mark_repeats)
         os.path.join(HERE, "csrc", "sdx_route.hip"),     # payload routes (sdx_route_lines)
         os.path.join(HERE, "csrc", "sdx_profile.hip"),   # receiver profiles (sdx_filter_records)
+        os.path.join(HERE, "csrc", "sdx_dispatch.hip"),  # dispatch rules (sdx_dispatch_records)
         os.path.join(HERE, "csrc", "sdx_units.hip"),     # unit-level helpers (sdx_units)
         os.path.join(HERE, "csrc", "sdx_exchange.hip"),  # multi-GPU exchange packing (sdx_exchange_pack)
         os.path.join(HERE, "csrc", "sdx_group.hip"),     # MU/MS message grouping (k_sig + radix sort)
@@ -34,6 +35,7 @@ DEPS = [*SRCS, os.path.join(HERE, "csrc", "sdx_device.h"), os.path.join(HERE, "c
         os.path.join(HERE, "csrc", "sdx_repeat_layout.h"),  # sdx_mark_repeats' buffer layout (sdx_repeat.hip)
         os.path.join(HERE, "csrc", "sdx_route_layout.h"),   # the route table's blob + validator (sdx_route.hip)
         os.path.join(HERE, "csrc", "sdx_profile_layout.h"),  # the profile table's blob + validator (sdx_profile.hip)
+        os.path.join(HERE, "csrc", "sdx_dispatch_layout.h"),  # sdx_dispatch_rules' validator (sdx_dispatch.hip)
         os.path.join(os.path.dirname(HERE), "include", "sdx.h"),
         os.path.join(os.path.dirname(HERE), "include", "sdx_bank.h")]
 

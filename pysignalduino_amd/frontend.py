@@ -353,7 +353,7 @@ class SignalParser:
 
     def parse_lines(self, lines: Sequence[Union[str, bytes]], collapse_repeats: bool = False, times=None,
                     repeat_window: Optional[float] = None, sources=None,
-                    profiles=None) -> List[Union[List[DecodedMessage], Exception]]:
+                    profiles=None, dispatch=None) -> List[Union[List[DecodedMessage], Exception]]:
         """Batch form of parse_line: one upload, one parse launch, one launch per demodulation
         variant, one read-back.  Returns one DecodedMessage list per line (or the ContractError
         for a line outside the device contract).  ``collapse_repeats``: a line that repeats the
@@ -365,8 +365,14 @@ class SignalParser:
         the window's anchor per source, the times non-decreasing within a source.  ``profiles`` (a
         profiles.ReceiverProfiles, a Profile or a list of them): every line keeps only the messages
         whose protocol its source's profile enables (``sources``: the ids, also without collapse_repeats; a table
-        of one source needs none) -- filtered on the device (sdx_filter_records) before anything is read back."""
+        of one source needs none) -- filtered on the device (sdx_filter_records) before anything is read back.
+        ``dispatch`` (a dispatch.DispatchRules, or True for FHEM's defaults): every line's list reduced
+        by the dispatch rules -- at most ``max_repeat`` messages of one protocol in a row, a message equal to the one
+        before it dropped -- on the device (sdx_dispatch_records), behind the profile pass and in front of
+        ``collapse_repeats``; a line's first message always stays."""
+        from .dispatch import as_rules
         from .profiles import as_profiles
+        dispatch = as_rules(dispatch)
         profiles = as_profiles(profiles)
         sources = self._source_args(collapse_repeats, sources, len(lines), profiles)
         times, w = self._window_args(collapse_repeats, times, repeat_window, len(lines), sources)
@@ -374,7 +380,7 @@ class SignalParser:
             return self._collapsed([], collapse_repeats)
         data, offsets, bad = pack_lines(lines)
         return self._collapsed(self._objects(lines, LineBatch(self.protocols._ensure(), data, offsets), offsets, bad,
-                                             len(data), profiles, sources), collapse_repeats, times, w,
+                                             len(data), profiles, sources, dispatch), collapse_repeats, times, w,
                                sources if collapse_repeats else None)
 
     def _collapsed(self, out: list, collapse: bool, times=None, window_us=None, sources=None) -> list:
@@ -384,10 +390,12 @@ class SignalParser:
             self.last_repeat_mask = collapse_objects(out, times, window_us, sources=sources)
         return out
 
-    def _objects(self, lines, lb: LineBatch, offsets: np.ndarray, bad: dict, nbytes: int, profiles=None, sources=None):
+    def _objects(self, lines, lb: LineBatch, offsets: np.ndarray, bad: dict, nbytes: int, profiles=None, sources=None,
+                 dispatch=None):
         """parse_lines from the uploaded batch on: ``lines`` indexable (lines[i] = line i's text),
         ``offsets`` the host copy of lb.offsets, ``nbytes`` = offsets[n].  ``profiles`` / ``sources``: the
-        launches' results go through sdx_filter_records before the objects are built from them."""
+        launches' results go through sdx_filter_records before the objects are built from them; ``dispatch`` (a
+        dispatch.DispatchRules): then through sdx_dispatch_records."""
         n = len(lines)
         eng = self.protocols._ensure()
         bk = self.protocols._bank
@@ -412,6 +420,8 @@ class SignalParser:
                                 rec_cap=len(bk.mn_pids) * nmn + 1024, heap_cap=int(4 * nbytes + 64 * nmn + 65536))
         if profiles is not None and res:
             res = eng.filter_fetched(profiles, res, n, sources)
+        if dispatch is not None and res:
+            res = eng.dispatch_fetched(dispatch, res, n)
         # read-back of the per-line fields the Python objects need
         kind = lb.kind[:n].cpu().numpy()
         status = lb.status[:n].cpu().numpy()
@@ -465,6 +475,8 @@ class SignalParser:
                                            gheap.tobytes(), abs(float(gvals[j, max(0, int(gcps[j]))])))
                 if profiles is not None and isinstance(g, list):   # the general path's lists are built on the host
                     g = profiles.filter(bk, 0 if sources is None else int(sources[i]), gname, g)
+                if dispatch is not None and isinstance(g, list):
+                    g = dispatch.reduce(bk, gname, g)
                 out.append(g)
                 continue
             if st != runtime.LS_OK or name not in res:
@@ -671,19 +683,12 @@ class SignalParser:
         return self._texts(lines, LineBatch(self.protocols._ensure(), data, offsets), bad, len(data), collapse_repeats,
                            times, w, sources, routes=table, drop_unrouted=drop_unrouted, match_any=any_, profiles=profiles)
 
-    def _texts(self, lines, lb: LineBatch, bad: dict, nbytes: int, collapse: bool = False, times=None,
-               window_us: Optional[int] = None, sources=None, routes=None, drop_unrouted: bool = False,
-               match_any: bool = False, profiles=None):
-        """parse_lines_json from the uploaded batch on (``lines`` and ``nbytes`` as in _objects).  ``routes``
-        (a routes.RouteTable; parse_lines_routed): every text becomes (route, text), see there; ``match_any``:
-        its route_match="any".  ``profiles`` (a profiles.ReceiverProfiles; ``sources``: the ids, or None for its
-        source 0): every kind's launch output goes through sdx_filter_records before anything else reads it."""
-        n = len(lines)
-        eng = self.protocols._ensure()
+    # -- what the JSON paths share: one launch set per kind, its outputs left on the device ------------------
+    def _json_jobs(self, lb: LineBatch, nbytes: int):
+        """-> (per kind with lines: (kind, rec_cap, heap_cap, json_cap, launches), the pulse batch); the batch is
+        launched already."""
         bk = self.protocols._bank
-        lb.launch()
         sels, cnt = lb.selections()
-        lo = {"meta": lb.meta, "pat_val": lb.pat_val, "cp_slot": lb.cp_slot}
         pb = lb.pulse_batch()
         jobs = []
         if cnt[runtime.SEL_MU_SHORT] or cnt[runtime.SEL_MU_LONG]:
@@ -702,41 +707,87 @@ class SignalParser:
             k = int(cnt[runtime.SEL_MN])
             jobs.append((runtime.KIND_MN, len(bk.mn_pids) * k + 1024, int(4 * nbytes + 64 * k + 65536),
                          int(6 * nbytes + 400 * k + 65536), [(lb.mn_batch(), sels[runtime.SEL_MN], False)]))
+        return jobs, pb
+
+    def _demodulate(self, n: int, kind, launches, rec_cap, heap_cap, elig):
+        eng = self.protocols._ensure()
+        work = eng.pulses_work_bytes(n) if kind in (runtime.KIND_MU, runtime.KIND_MS) else 0
+        out = eng.alloc_out(n, rec_cap, heap_cap, work)  # MU/MS: grouped order + spill room
+        for bd, sel, long_v in launches:
+            if not sel.numel():
+                continue
+            if kind == runtime.KIND_MN:
+                eng.launch_mn(bd, out, elig=elig, sel=sel)
+            elif kind == runtime.KIND_MC:
+                eng.launch_mc(bd, out, sel=sel)
+            else:
+                eng.launch_pulses(kind, bd, out, sel=sel, long_variant=long_v)
+        return out
+
+    def _rerun_tile_overflows(self, n: int, pb, kind, out, rec_cap, heap_cap):
+        """An MU/MS launch whose cursor[2] is 2: tiles overflowed their on-chip staging and found no
+        spill region left (ST_OVF_TILE), which larger outputs cannot cure.  Those messages re-run on
+        the long variant into an overlay, as Engine.run does; returns the launch and the overlay as
+        one output (merge_overlay), which the repeat pass and the serialiser read like any other."""
+        eng = self.protocols._ensure()
+        st = out["desc"][: 8 * n].view(-1, 8)[:, 6].cpu().numpy()
+        redo = np.nonzero(st == runtime.ST_OVF_TILE)[0].astype(np.int32)
+        for _attempt in range(4):
+            ov = eng.rerun_overlay(kind, pb, redo, rec_cap, heap_cap)
+            c = ov["cursor"].cpu().numpy()
+            if c[2] & 2:
+                raise RuntimeError("result staging overflow persists (pathological message)")
+            if not c[2]:
+                return eng.merge_overlay(out, ov, redo)
+            rec_cap, heap_cap = 4 * rec_cap, 4 * heap_cap
+        raise RuntimeError("result capacity overflow persists")
+
+    def _demodulate_kept(self, n: int, pb, jobs, elig, host_rows: List[int]):
+        """Every kind's launch, grown and re-run until nothing but host rows is left over: -> [(kind, out, json_cap)]
+        with the outputs on the device; MC frames the device hands over are appended to ``host_rows``."""
+        kept = []
+        for kind, rec_cap, heap_cap, json_cap, launches in jobs:
+            for _attempt in range(4):
+                out = self._demodulate(n, kind, launches, rec_cap, heap_cap, elig)
+                c1 = out["cursor"].cpu().numpy()
+                if kind == runtime.KIND_MC and c1[2] == 2:   # frames of > 128 hex characters: host rows
+                    sel = launches[0][1]
+                    st = out["desc"][: 8 * n].view(-1, 8)[:, 6][sel.long()].cpu().numpy()
+                    host_rows.extend(int(i) for i in sel.cpu().numpy()[st == runtime.ST_OVF_TILE])
+                    break
+                if kind in (runtime.KIND_MU, runtime.KIND_MS) and c1[2] == 2:   # only tile overflows are left: not a capacity matter
+                    out = self._rerun_tile_overflows(n, pb, kind, out, rec_cap, heap_cap)
+                    break
+                if not c1[2]:
+                    break
+                rec_cap, heap_cap = 4 * rec_cap, 4 * heap_cap   # bit 0: the outputs overflowed
+            else:
+                raise RuntimeError("result capacity overflow persists")
+            kept.append((kind, out, json_cap))
+        return kept
+
+    def _texts(self, lines, lb: LineBatch, bad: dict, nbytes: int, collapse: bool = False, times=None,
+               window_us: Optional[int] = None, sources=None, routes=None, drop_unrouted: bool = False,
+               match_any: bool = False, profiles=None):
+        """parse_lines_json from the uploaded batch on (``lines`` and ``nbytes`` as in _objects).  ``routes``
+        (a routes.RouteTable; parse_lines_routed): every text becomes (route, text), see there; ``match_any``:
+        its route_match="any".  ``profiles`` (a profiles.ReceiverProfiles; ``sources``: the ids, or None for its
+        source 0): every kind's launch output goes through sdx_filter_records before anything else reads it."""
+        n = len(lines)
+        eng = self.protocols._ensure()
+        lb.launch()
+        lo = {"meta": lb.meta, "pat_val": lb.pat_val, "cp_slot": lb.cp_slot}
+        jobs, pb = self._json_jobs(lb, nbytes)
         elig = self._mn_elig(profiles)
         rsources = sources if collapse else None   # the repeat pass's ids: without collapse the ids are the profiles' alone
         texts: List[Any] = [None] * n
         host_rows: List[int] = []   # lines whose text is built from parse_lines' objects (general paths)
 
         def demodulate(kind, launches, rec_cap, heap_cap):
-            work = eng.pulses_work_bytes(n) if kind in (runtime.KIND_MU, runtime.KIND_MS) else 0
-            out = eng.alloc_out(n, rec_cap, heap_cap, work)  # MU/MS: grouped order + spill room
-            for bd, sel, long_v in launches:
-                if not sel.numel():
-                    continue
-                if kind == runtime.KIND_MN:
-                    eng.launch_mn(bd, out, elig=elig, sel=sel)
-                elif kind == runtime.KIND_MC:
-                    eng.launch_mc(bd, out, sel=sel)
-                else:
-                    eng.launch_pulses(kind, bd, out, sel=sel, long_variant=long_v)
-            return out
+            return self._demodulate(n, kind, launches, rec_cap, heap_cap, elig)
 
         def rerun_tile_overflows(kind, out, rec_cap, heap_cap):
-            """An MU/MS launch whose cursor[2] is 2: tiles overflowed their on-chip staging and found no
-            spill region left (ST_OVF_TILE), which larger outputs cannot cure.  Those messages re-run on
-            the long variant into an overlay, as Engine.run does; returns the launch and the overlay as
-            one output (merge_overlay), which the repeat pass and the serialiser read like any other."""
-            st = out["desc"][: 8 * n].view(-1, 8)[:, 6].cpu().numpy()
-            redo = np.nonzero(st == runtime.ST_OVF_TILE)[0].astype(np.int32)
-            for _attempt in range(4):
-                ov = eng.rerun_overlay(kind, pb, redo, rec_cap, heap_cap)
-                c = ov["cursor"].cpu().numpy()
-                if c[2] & 2:
-                    raise RuntimeError("result staging overflow persists (pathological message)")
-                if not c[2]:
-                    return eng.merge_overlay(out, ov, redo)
-                rec_cap, heap_cap = 4 * rec_cap, 4 * heap_cap
-            raise RuntimeError("result capacity overflow persists")
+            return self._rerun_tile_overflows(n, pb, kind, out, rec_cap, heap_cap)
 
         def serialize(kind, out, json_cap, skip=None):
             """The launch's texts into a fresh buffer, grown until they fit: (buffers, bytes used)."""
@@ -768,25 +819,7 @@ class SignalParser:
         if collapse or routes is not None or profiles is not None:
             # every kind's launch first (their outputs stay on the device), then ONE sdx_mark_repeats over
             # them, then the serialiser with the mask: a repeat is never turned into text
-            kept = []
-            for kind, rec_cap, heap_cap, json_cap, launches in jobs:
-                for _attempt in range(4):
-                    out = demodulate(kind, launches, rec_cap, heap_cap)
-                    c1 = out["cursor"].cpu().numpy()
-                    if kind == runtime.KIND_MC and c1[2] == 2:   # frames of > 128 hex characters: host rows
-                        sel = launches[0][1]
-                        st = out["desc"][: 8 * n].view(-1, 8)[:, 6][sel.long()].cpu().numpy()
-                        host_rows.extend(int(i) for i in sel.cpu().numpy()[st == runtime.ST_OVF_TILE])
-                        break
-                    if kind in pulses and c1[2] == 2:   # only tile overflows are left: not a capacity matter
-                        out = rerun_tile_overflows(kind, out, rec_cap, heap_cap)
-                        break
-                    if not c1[2]:
-                        break
-                    rec_cap, heap_cap = 4 * rec_cap, 4 * heap_cap   # bit 0: the outputs overflowed
-                else:
-                    raise RuntimeError("result capacity overflow persists")
-                kept.append((kind, out, json_cap))
+            kept = self._demodulate_kept(n, pb, jobs, elig, host_rows)
             if kept and profiles is not None:
                 # right behind the launches: every line keeps the records its source's profile enables, compacted
                 # in line order; everything below reads the filtered outputs (they share the launches' heaps)
@@ -922,8 +955,171 @@ class SignalParser:
                     texts[i] = None if drop_unrouted and route[i] < 0 else (int(route[i]), x)
         return texts
 
+    # -- every message of a line -------------------------------------------------------
+    def parse_lines_json_all(self, lines: Sequence[Union[str, bytes]], dispatch=None, profiles=None, sources=None,
+                             collapse_repeats: bool = False, times=None,
+                             repeat_window: Optional[float] = None) -> List[Union[List[str], Exception]]:
+        """Per line, the MQTT texts of EVERY message it decodes to, in the reference's order:
+        ``[MqttPublisher._message_to_json(m) for m in parse_line(line)]``, [] where nothing decodes, the
+        ContractError in its slot as elsewhere -- FHEM dispatches every message of a line, where
+        parse_lines_json publishes ``decoded[0]`` alone.  The texts are built on the device, one per result
+        record (sdx_serialize_json, first_only = 0).  ``dispatch`` (a dispatch.DispatchRules, True for FHEM's
+        defaults): every list reduced by the dispatch rules first (sdx_dispatch_records) -- at most ``max_repeat``
+        messages of one protocol in a row, a message equal to the one before it dropped unless its protocol
+        carries ``dispatchequals``; None: every message.  ``profiles`` / ``sources``: receiver profiles as
+        parse_lines_json takes them, in front of the rules (a disabled protocol never runs, so it never counts).
+        ``collapse_repeats`` (``times``, ``repeat_window``, ``sources`` as parse_lines_json): a line that repeats
+        the previous result-bearing line's first message gives []; the mask is left in ``last_repeat_mask``.  The
+        first text of a line's list is always parse_lines_json's text of that line."""
+        from .dispatch import as_rules
+        from .profiles import as_profiles
+        dispatch = as_rules(dispatch)
+        profiles = as_profiles(profiles)
+        sources = self._source_args(collapse_repeats, sources, len(lines), profiles)
+        times, w = self._window_args(collapse_repeats, times, repeat_window, len(lines), sources)
+        if len(lines) == 0:
+            if collapse_repeats:
+                self.last_repeat_mask = np.zeros(0, np.uint8)
+            return []
+        data, offsets, bad = pack_lines(lines)
+        return self._texts_all(lines, LineBatch(self.protocols._ensure(), data, offsets), bad, len(data), dispatch, profiles,
+                               sources, collapse_repeats, times, w)
+
+    def parse_bytes_json_all(self, data, final: bool = True, dispatch=None, profiles=None, collapse_repeats: bool = False):
+        """parse_lines_json_all over a raw read buffer (see parse_bytes; the same return forms)."""
+        from .dispatch import as_rules
+        from .profiles import as_profiles
+        dispatch = as_rules(dispatch)
+        profiles = as_profiles(profiles)
+        self._source_args(collapse_repeats, None, 0, profiles)
+        lines, lb, tail = self._split_bytes(data, final)
+        if collapse_repeats:
+            self.last_repeat_mask = np.zeros(0, np.uint8)
+        out = (self._texts_all(lines, lb, {}, int(lines.offsets[-1]), dispatch, profiles, None, collapse_repeats)
+               if len(lines) else [])
+        return out if final else (out, tail)
+
+    def _texts_all(self, lines, lb: LineBatch, bad: dict, nbytes: int, dispatch=None, profiles=None, sources=None,
+                   collapse: bool = False, times=None, window_us: Optional[int] = None):
+        """parse_lines_json_all from the uploaded batch on (``lines`` and ``nbytes`` as in _objects): every kind's
+        launch, the profile pass, the dispatch pass, the repeat pass, then the serialiser over every record of what
+        is left -- line g's texts stand at the record indices [rec_begin, rec_begin + n_rec) of its descriptor."""
+        n = len(lines)
+        eng = self.protocols._ensure()
+        lb.launch()
+        lo = {"meta": lb.meta, "pat_val": lb.pat_val, "cp_slot": lb.cp_slot}
+        jobs, pb = self._json_jobs(lb, nbytes)
+        rsources = sources if collapse else None
+        out: List[Any] = [[] for _ in range(n)]
+        host_rows: List[int] = []   # lines whose texts are built from parse_lines' objects (general paths)
+        kept = self._demodulate_kept(n, pb, jobs, self._mn_elig(profiles), host_rows)
+        ins_of = lambda ks: [eng.json_in(kind, o, lo, n) for kind, o, _ in ks]   # noqa: E731
+        if kept and profiles is not None:
+            pbufs = eng.alloc_profiles(n, [o for _, o, _ in kept])
+            d_src = None if sources is None else eng.torch.from_numpy(np.ascontiguousarray(sources, np.int32)).to(eng.dev)
+            fouts = eng.filter_records(profiles, ins_of(kept), n, pbufs, source=d_src)
+            kept = [(kind, fo, json_cap) for (kind, _, json_cap), fo in zip(kept, fouts)]
+        if kept and dispatch is not None:
+            dbufs = eng.alloc_dispatch(n, [o for _, o, _ in kept])
+            douts = eng.dispatch_records(dispatch, ins_of(kept), n, dbufs)
+            kept = [(kind, do, json_cap) for (kind, _, json_cap), do in zip(kept, douts)]
+        rep = np.zeros(n, np.uint8)
+        rbufs = None
+        if collapse:
+            from .repeats import RepeatPass, apply_mask, count_sources, objects_key, text_key
+            rpass = RepeatPass(eng, window_us, None if sources is None else count_sources(sources))
+        if kept:
+            skip = None
+            if collapse:   # the mask of the lines' first records: a repeat line loses every record's text
+                rbufs = rpass.alloc(n, pinned=False)
+                rpass.enqueue(rbufs, ins_of(kept), n, times=times, sources=rsources)
+                skip = rbufs.mask
+            for kind, o, json_cap in kept:
+                self._take_texts_all(out, n, kind, o, lo, 2 * json_cap, skip)
+            if collapse:
+                rep = rbufs.mask[:n].cpu().numpy()
+        status = lb.status[:n].cpu().numpy()
+        kinds = lb.kind[:n].cpu().numpy()
+        exact = (status == runtime.LS_UNSUPPORTED) & ((kinds == runtime.LINE_MU) | (kinds == runtime.LINE_MS))
+        grows = [int(i) for i in np.nonzero((status == runtime.LS_GENERAL) | exact)[0] if int(i) not in bad] + host_rows
+        resolved = set()
+        has_text = np.fromiter((bool(x) for x in out), bool, n) if collapse else None
+        host_keys = {}   # collapse: the host-resolved rows' keys (None: no result)
+
+        def kw_for(rows):
+            kw = {} if dispatch is None else {"dispatch": dispatch}
+            if profiles is not None:
+                kw.update(profiles=profiles, sources=None if sources is None else [int(sources[i]) for i in rows])
+            return kw
+
+        if grows:  # host-resolved lines (rare): their objects through parse_lines, every message's text on the host
+            for i, g in zip(grows, self.parse_lines([lines[i] for i in grows], **kw_for(grows))):
+                if collapse:
+                    host_keys[i] = objects_key(g)
+                if exact[i]:
+                    if isinstance(g, ContractError):
+                        continue   # still unsupported: reported below, under its index in this batch
+                    resolved.add(i)
+                out[i] = g if isinstance(g, BaseException) else [
+                    json.dumps({"protocol_id": m.protocol_id, "payload": m.payload, "metadata": m.metadata}, indent=4) for m in g]
+        for i in range(n):
+            if i in bad:
+                out[i] = bad[i]
+            elif int(status[i]) == runtime.LS_UNSUPPORTED and i not in resolved:
+                out[i] = ContractError(f"line {i} is outside the device contract of the front end "
+                                       f"(kind {_KIND_NAME.get(int(kinds[i]), '?')})")
+        if collapse:
+            fetched = {}
+
+            def one_list(i):    # the line's texts on their own
+                return self.parse_lines_json_all([lines[i]], **kw_for([i]))[0]
+
+            def fetch_key(i):   # a flagged line whose run head the host does not know: the batch API
+                fetched[i] = one_list(i)
+                return text_key(_KIND_NAME[int(kinds[i])], fetched[i][0]) if isinstance(fetched[i], list) and fetched[i] else None
+
+            dev_key_of = lambda i: text_key(_KIND_NAME[int(kinds[i])], out[i][0])   # noqa: E731
+            mask = rpass.exact_mask(rbufs, rep, has_text, dev_key_of, host_keys, fetch=fetch_key, times=times,
+                                    sources=rsources)
+
+            def drop(i):         # a host-resolved repeat, or a repeat of a host-resolved line
+                out[i] = []
+
+            def republish(i):    # the device skipped it, but its predecessor was a host row
+                out[i] = fetched[i] if i in fetched else one_list(i)
+            apply_mask(mask, rep, host_keys, drop, republish)
+            self.last_repeat_mask = mask
+        return out
+
+    def _take_texts_all(self, out: list, n: int, kind, o, lo, json_cap: int, skip) -> None:
+        """One kind's texts, one per record (first_only = 0), into a fresh buffer grown until they fit; then per line
+        with an OK descriptor the texts of its records, in order, into ``out``."""
+        eng = self.protocols._ensure()
+        items = max(int(o["rec_cap"]), 1)
+        for _attempt in range(5):
+            jo = eng.alloc_json(items, json_cap)
+            jo["len"].zero_()
+            eng.launch_json(kind, o, lo, n, jo, first_only=0, skip=skip)
+            c = jo["cursor"].cpu().numpy()
+            if not c[1]:
+                break
+            json_cap *= 4
+        else:
+            raise RuntimeError("JSON capacity overflow persists")
+        desc = o["desc"][: 8 * n].cpu().numpy().view(runtime.DESC_DT)
+        rows = np.nonzero((desc["status"] == runtime.ST_OK) & (desc["n_rec"] > 0))[0]
+        if not len(rows):
+            return
+        total = min(int(o["cursor"][0].item()), items)
+        lens = jo["len"][:total].cpu().numpy().tolist()
+        offs = jo["off"][:total].cpu().numpy().tolist()
+        blob = jo["json"][: int(c[0])].cpu().numpy().tobytes().decode("ascii")
+        begin, count = desc["rec_begin"][rows].tolist(), desc["n_rec"][rows].tolist()
+        for i, b, k in zip(rows.tolist(), begin, count):
+            out[i] = [blob[offs[r]: offs[r] + lens[r]] for r in range(b, b + k) if lens[r]]
+
     # -- byte-stream input ---------------------------------------------------------------------------
-    def parse_bytes(self, data, final: bool = True, collapse_repeats: bool = False, profiles=None):
+    def parse_bytes(self, data, final: bool = True, collapse_repeats: bool = False, profiles=None, dispatch=None):
         """parse_lines over a transport's raw read buffer (bytes-like): the bytes are uploaded and split
         into lines on the device (sdx_split_lines: every '\\n' ends a line, as StreamReader.readline(),
         signalduino/transport.py:113-123).  ``final=True``: bytes after the last '\\n' are the last line
@@ -931,12 +1127,16 @@ class SignalParser:
         (that list for the terminated lines, the unterminated tail as bytes) -- prepend the tail to the
         next buffer.  There is no ``repeat_window`` here or in parse_bytes_json: one call has no per-line
         arrival times (LineStream.submit_bytes takes one per read buffer).  ``profiles``: receiver profiles as
-        parse_lines takes them, for the one receiver the buffer was read from (a table of one source)."""
+        parse_lines takes them, for the one receiver the buffer was read from (a table of one source).  ``dispatch``:
+        the dispatch rules as parse_lines takes them."""
+        from .dispatch import as_rules
         from .profiles import as_profiles
+        dispatch = as_rules(dispatch)
         profiles = as_profiles(profiles)
         self._source_args(collapse_repeats, None, 0, profiles)
         lines, lb, tail = self._split_bytes(data, final)
-        out = self._objects(lines, lb, lines.offsets, {}, int(lines.offsets[-1]), profiles) if len(lines) else []
+        out = (self._objects(lines, lb, lines.offsets, {}, int(lines.offsets[-1]), profiles, dispatch=dispatch)
+               if len(lines) else [])
         out = self._collapsed(out, collapse_repeats)
         return out if final else (out, tail)
 

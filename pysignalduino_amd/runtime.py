@@ -53,7 +53,7 @@ EXPORTED = ["sdx_abi_version", "sdx_last_error", "sdx_source_hash", "sdx_layout_
             "sdx_repeat_sources_scratch_bytes", "sdx_route_table_create", "sdx_route_table_destroy",
             "sdx_route_table_lds_routes", "sdx_route_lines", "sdx_route_records", "sdx_route_skip",
             "sdx_profile_table_create", "sdx_profile_table_destroy", "sdx_profile_check", "sdx_profile_scratch_bytes",
-            "sdx_filter_records"]
+            "sdx_filter_records", "sdx_dispatch_scratch_bytes", "sdx_dispatch_records"]
 REPEAT_SOURCES_MAX = 4096   # SDX_REPEAT_SOURCES_MAX
 # sdx_repeat_source_entry (csrc/sdx_repeat_layout.h): a source's slot header after a chunk + its last result-bearing line
 REPEAT_SOURCE_ENTRY = np.dtype([("valid", "<u4"), ("kind", "<u4"), ("proto", "<u4"), ("len", "<u4"), ("t", "<i8"),
@@ -110,6 +110,12 @@ class SdxJsonIn(Structure):
 class SdxJsonOut(Structure):
     _fields_ = [("json_dev", c_void_p), ("off_dev", c_void_p), ("len_dev", c_void_p), ("cursor_dev", c_void_p),
                 ("json_cap", c_uint32), ("res", c_uint32)]
+
+
+class SdxDispatchRules(Structure):
+    """sdx_dispatch_rules (include/sdx.h), 152 bytes: dispatch.DispatchRules.struct fills it."""
+    _fields_ = [("keep_equal", (ctypes.c_uint64 * 4) * 4), ("max_repeat", c_int32 * 4), ("drop_equal", c_int32),
+                ("res", c_int32)]
 
 
 class SdxUnitBatch(Structure):
@@ -303,6 +309,11 @@ def load_library(path: Optional[str] = None):
     lib.sdx_filter_records.argtypes = [c_void_p, c_void_p, POINTER(SdxJsonIn), c_int, c_int32, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p]
     lib.sdx_filter_records.restype = c_int
+    lib.sdx_dispatch_scratch_bytes.argtypes = [c_int, c_int32]
+    lib.sdx_dispatch_scratch_bytes.restype = c_size_t
+    lib.sdx_dispatch_records.argtypes = [c_void_p, POINTER(SdxDispatchRules), POINTER(SdxJsonIn), c_int, c_int32, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.sdx_dispatch_records.restype = c_int
     lib.sdx_parse_lines.argtypes = [POINTER(SdxLines), POINTER(SdxLinesOut), c_void_p]
     lib.sdx_parse_lines.restype = c_int
     lib.sdx_select_lines.argtypes = [POINTER(SdxLinesOut), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
@@ -1045,6 +1056,72 @@ class Engine:
         bufs = self.alloc_profiles(n, outs)
         src = None if sources is None else t.from_numpy(np.ascontiguousarray(sources, np.int32)).to(self.dev)
         f = self.filter_records(table, ins, n, bufs, source=src)
+        out = dict(res)
+        for name, o in zip(names, f):
+            total = int(o["cursor"][0].item())
+            out[name] = (o["desc"][: n * DESC_DT.itemsize].cpu().numpy().view(DESC_DT).copy(),
+                         o["rec"][: total * RES_DT.itemsize].cpu().numpy().view(RES_DT).copy(), res[name][2])
+        return out
+
+    # -- dispatch rules (sdx_dispatch_records) ----------------------------------------
+    def alloc_dispatch(self, n: int, outs):
+        """The buffers of dispatch_records for chunks of up to n lines whose launches write ``outs``: as
+        alloc_profiles', with sdx_dispatch_scratch_bytes of scratch."""
+        bufs = self.alloc_profiles(n, outs)
+        size = int(self.lib.sdx_dispatch_scratch_bytes(max(len(outs), 1), max(int(n), 1)))
+        bufs["scratch"] = self.torch.empty(size, dtype=self.torch.uint8, device=self.dev)
+        return bufs
+
+    def dispatch_records(self, rules, json_ins, n: int, bufs, stream=None, rec_caps=None):
+        """sdx_dispatch_records on ``stream`` (default: the current one; no host sync): the launch outputs behind
+        ``json_ins`` (json_in, one per kind) with every line keeping only the records the dispatch rules keep
+        (``rules``: a dispatch.DispatchRules, True for the defaults, or a filled SdxDispatchRules), compacted in line
+        order into ``bufs`` (alloc_dispatch's).  ``rec_caps``: the record capacities to declare (default: the
+        buffers').  Returns bufs["outs"]: reduced outs shaped like alloc_out's, sharing the launches' heaps."""
+        n = int(n)
+        if not isinstance(rules, SdxDispatchRules):
+            from .dispatch import as_rules
+            rules = as_rules(rules)
+            if rules is None:
+                raise ValueError("dispatch_records: no rules")
+            rules = rules.struct(self.bank)
+        outs = bufs["outs"]
+        if len(outs) != len(json_ins):
+            raise ValueError("dispatch_records: one output per kind")
+        k = max(len(outs), 1)
+        caps = [o["rec_cap"] for o in outs] if rec_caps is None else [int(c) for c in rec_caps]
+        for o, c in zip(outs, caps):
+            if o["rec"].numel() < c * RES_DT.itemsize:
+                raise ValueError("dispatch_records: a record buffer is smaller than its declared capacity")
+        darr = (c_void_p * k)(*[_ptr(o["desc"]) for o in outs])
+        rarr = (c_void_p * k)(*[_ptr(o["rec"]) for o in outs])
+        carr = (c_void_p * k)(*[_ptr(o["cursor"]) for o in outs])
+        caparr = (ctypes.c_uint32 * k)(*caps)
+        need = int(self.lib.sdx_dispatch_scratch_bytes(k, n)) if 1 <= len(outs) <= 4 and n >= 0 else 0
+        self._mark("dispatch_records",
+                   lambda bank, arr, k_, n_, *a: self.lib.sdx_dispatch_records(bank, ctypes.byref(rules), arr, k_, n_, *a),
+                   json_ins, n, [(bufs["scratch"], need)] + [(o["desc"], 8 * n) for o in outs],
+                   (darr, rarr, caparr, carr, _ptr(bufs["scratch"])), stream)
+        return outs
+
+    def dispatch_fetched(self, rules, res: dict, n: int) -> dict:
+        """dispatch_records for results already on the host (run()'s), as filter_fetched -- but the heaps go up too:
+        this pass reads payloads.  The heaps themselves stay as they are (payload offsets are unchanged)."""
+        t = self.torch
+        names = [k for k in ("MU", "MS", "MC", "MN") if k in res]
+        up = lambda a: t.from_numpy(np.frombuffer(a.tobytes(), np.uint8).copy()).to(self.dev)   # noqa: E731
+        outs, ins = [], []
+        for name in names:
+            desc, rec, heap = res[name]
+            o = {"desc": up(desc) if len(desc) else t.zeros(8, dtype=t.uint8, device=self.dev),
+                 "rec": up(rec) if len(rec) else t.zeros(RES_DT.itemsize, dtype=t.uint8, device=self.dev),
+                 "heap": up(heap) if len(heap) else t.zeros(16, dtype=t.uint8, device=self.dev),
+                 "cursor": t.tensor([len(rec), 0, 0, 0], dtype=t.int32, device=self.dev), "rec_cap": len(rec),
+                 "heap_cap": len(heap), "n": n}
+            outs.append(o)
+            ins.append(self.json_in(("MU", "MS", "MC", "MN").index(name), o, {"meta": o["desc"]}, n))
+        bufs = self.alloc_dispatch(n, outs)
+        f = self.dispatch_records(rules, ins, n, bufs)
         out = dict(res)
         for name, o in zip(names, f):
             total = int(o["cursor"][0].item())
