@@ -1,4 +1,4 @@
-"""Compile the bank's ``modulematch`` regexes into search DFAs for the device.
+r"""Compile the bank's ``modulematch`` regexes into search DFAs for the device.
 
 The reference filters every MU result with ``re.search(modulematch, payload)``
 (sd_protocols/message_unsynced.py:277-280).  The device cannot run Python's
@@ -9,11 +9,20 @@ patterns.  The device walks the payload once: state = trans[state][cls[b]].
 
 Supported syntax = the subset the bank uses plus the usual neighbours:
 literals and escapes, ``.``, ``[...]`` classes (ranges, negation), ``(...)``
-``(?:...)`` groups, ``|``, ``* + ? {m} {m,} {m,n}`` (lazy suffix accepted:
+``(?:...)`` groups, ``|``, ``* + ? {m} {m,} {m,n} {,n}`` (lazy suffix accepted:
 laziness cannot change whether a match exists), ``^`` and ``$``.  Anything
 else raises NotImplementedError at bank-compile time (loud, never a silent
-divergence).  ``tests/test_regex_dfa.py`` cross-checks every compiled
-pattern against ``re.search`` on random payload-like strings.
+divergence): that includes what ``re`` itself refuses -- a quantifier behind
+a quantified item (``a**``, ``a{2}{3}``; also ``a++`` and ``a*+``, which
+newer Pythons read as possessive), a quantifier on ``^`` or ``$`` or on
+nothing, ``{m,n}`` with n < m, a class range with a class escape as an
+endpoint (``[\w-z]``).  ``tests/test_regex_dfa.py`` cross-checks generated
+patterns (``tests/regex_corpus.py``) against ``re.search`` on strings over
+every byte value but the newline.
+
+The criterion is ``re`` on ``str``: a payload's bytes are its latin-1 text,
+so ``\w \W \s \S`` are the Unicode sets restricted to code points 0..255
+(``\w`` holds 0xE9, ``\s`` holds 0x1C-0x1F, 0x85 and 0xA0); ``\d`` is 0-9.
 
 ``$`` is compiled as end-of-payload only; Python's ``$`` also matches before
 a trailing newline, which a payload (bank pre/postamble + hex digits) never
@@ -25,8 +34,11 @@ from typing import Dict, FrozenSet, List, Optional, Sequence, Tuple
 
 ANY_BUT_NL = frozenset(b for b in range(256) if b != 10)
 DIGITS = frozenset(range(48, 58))
-WORD = frozenset(list(range(48, 58)) + list(range(65, 91)) + list(range(97, 123)) + [95])
-SPACE = frozenset([9, 10, 11, 12, 13, 32])
+# str-``re``'s \w and \s on code points 0..255 (str.isalnum() or "_"; str.isspace()), written out
+_WORD_RANGES = ((48, 57), (65, 90), (95, 95), (97, 122), (170, 170), (178, 179), (181, 181), (185, 186), (188, 190),
+                (192, 214), (216, 246), (248, 255))
+WORD = frozenset(b for lo, hi in _WORD_RANGES for b in range(lo, hi + 1))
+SPACE = frozenset(list(range(9, 14)) + list(range(28, 33)) + [133, 160])
 ACC_NOW = 1
 ACC_END = 2
 DEAD = 4   # no match reachable any more from this state
@@ -80,30 +92,36 @@ class _Parser:
             n = int(parts[1]) if parts[1] else None
         else:
             return None
+        if n is not None and n < m:
+            self.err("min repeat greater than max repeat")
         self.i = j + 1
         return m, n
 
+    def _quant_one(self):
+        """(m, n) of the quantifier at the cursor, consumed with its lazy ``?``; None if there is none."""
+        c = self.peek()
+        if c == "{":
+            q = self._quant_braces()
+            if q is None:
+                return None  # literal '{' handled by the next atom()
+        elif c is not None and c in "*+?":
+            self.take()
+            q = {"*": (0, None), "+": (1, None), "?": (0, 1)}[c]
+        else:
+            return None
+        if self.peek() == "?":  # lazy form: same match existence
+            self.take()
+        return q
+
     def quant(self, node):
-        while True:
-            c = self.peek()
-            if c == "*":
-                self.take()
-                node = ("rep", node, 0, None)
-            elif c == "+":
-                self.take()
-                node = ("rep", node, 1, None)
-            elif c == "?":
-                self.take()
-                node = ("rep", node, 0, 1)
-            elif c == "{":
-                q = self._quant_braces()
-                if q is None:
-                    return node  # literal '{' handled by the next atom()
-                node = ("rep", node, q[0], q[1])
-            else:
-                return node
-            if self.peek() == "?":  # lazy form: same match existence
-                self.take()
+        q = self._quant_one()
+        if q is None:
+            return node
+        if node[0] in ("bol", "eol"):
+            self.err("quantifier on an anchor")
+        if self._quant_one() is not None:  # re: "multiple repeat"; x++ / x*+ / x?+ are possessive from 3.11 on
+            self.err("quantifier on a quantified item")
+        return ("rep", node, q[0], q[1])
 
     def _escape_set(self, c):
         table = {"d": DIGITS, "w": WORD, "s": SPACE}
@@ -115,6 +133,8 @@ class _Parser:
             return frozenset([{"n": 10, "r": 13, "t": 9, "f": 12, "v": 11}[c]])
         if c.isalnum():
             self.err(f"unsupported escape \\{c}")
+        if ord(c) > 255:
+            self.err("non-latin-1 literal")
         return frozenset([ord(c)])
 
     def atom(self):
@@ -143,6 +163,11 @@ class _Parser:
             return ("set", self._escape_set(self.take()))
         if c in "*+?":
             self.err("nothing to repeat")
+        if c == "{":
+            self.i -= 1
+            if self._quant_braces() is not None:
+                self.err("nothing to repeat")
+            self.i += 1
         if ord(c) > 255:
             self.err("non-latin-1 literal")
         return ("set", frozenset([ord(c)]))
@@ -164,26 +189,36 @@ class _Parser:
             first = False
             self.take()
             if c == "\\":
+                if self.peek() is None:
+                    self.err("unterminated class")
                 lo_set = self._escape_set(self.take())
             else:
+                if ord(c) > 255:
+                    self.err("non-latin-1 literal")
                 lo_set = frozenset([ord(c)])
-            if self.peek() == "-" and self.i + 1 < len(self.p) and self.p[self.i + 1] != "]" and len(lo_set) == 1:
+            if self.peek() == "-" and self.i + 1 < len(self.p) and self.p[self.i + 1] != "]":
+                if len(lo_set) != 1:
+                    self.err("bad range: a class escape as an endpoint")
                 self.take()
                 hc = self.take()
                 if hc == "\\":
+                    if self.peek() is None:
+                        self.err("unterminated class")
                     hs = self._escape_set(self.take())
                     if len(hs) != 1:
-                        self.err("bad range")
+                        self.err("bad range: a class escape as an endpoint")
                     hi = next(iter(hs))
                 else:
                     hi = ord(hc)
                 lo = next(iter(lo_set))
+                if hi > 255:
+                    self.err("non-latin-1 literal")
                 if hi < lo:
                     self.err("bad range")
                 members.update(range(lo, hi + 1))
             else:
                 members.update(lo_set)
-        s = frozenset(b for b in members if b < 256)
+        s = frozenset(members)
         return frozenset(range(256)) - s if neg else s
 
 

@@ -1,12 +1,13 @@
-"""Payload routes: an ordered client list of (name, regex) pairs decides which consumer a
+r"""Payload routes: an ordered client list of (name, regex) pairs decides which consumer a
 decoded telegram concerns, as FHEM's dispatch does behind its equal-message drop.
 
 A :class:`RouteTable` compiles the list with ``regex_dfa.compile_bank_dfas`` into one search DFA per route
 over a shared byte-class alphabet and writes the blob the device walks (``sdx_route_lines``; the layout is
 ``csrc/sdx_route_layout.h``, the constants below mirror it).  For a payload: ``mask`` has bit r set iff
-``re.search(pattern_r, payload)`` finds a match, ``route`` is the lowest set bit or -1.  Payloads are
-matched as bytes (latin-1); a payload holds no newline, so ``$`` as regex_dfa compiles it and Python's
-agree.  :meth:`RouteTable.match` is the host restatement: it walks the same compiled tables, read back
+``re.search(pattern_r, payload)`` finds a match, ``route`` is the lowest set bit or -1.  A payload is
+matched as its latin-1 text (``re`` on ``str``: ``\w`` and ``\s`` are the Unicode sets on code points
+0..255, as regex_dfa writes them out); a payload holds no newline, so ``$`` as regex_dfa compiles it and
+Python's agree.  :meth:`RouteTable.match` is the host restatement: it walks the same compiled tables, read back
 out of the blob."""
 from __future__ import annotations
 
