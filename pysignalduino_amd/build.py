@@ -36,6 +36,7 @@ DEPS = [*SRCS, os.path.join(HERE, "csrc", "sdx_device.h"), os.path.join(HERE, "c
         os.path.join(HERE, "csrc", "sdx_route_layout.h"),   # the route table's blob + validator (sdx_route.hip)
         os.path.join(HERE, "csrc", "sdx_profile_layout.h"),  # the profile table's blob + validator (sdx_profile.hip)
         os.path.join(HERE, "csrc", "sdx_dispatch_layout.h"),  # sdx_dispatch_rules' validator (sdx_dispatch.hip)
+        os.path.join(HERE, "csrc", "sdx_compact.h"),     # count -> scan -> write of both record passes
         os.path.join(os.path.dirname(HERE), "include", "sdx.h"),
         os.path.join(os.path.dirname(HERE), "include", "sdx_bank.h")]
 

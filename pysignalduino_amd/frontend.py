@@ -230,6 +230,12 @@ def _contract(i: int, name) -> ContractError:
                          "(include/sdx.h SDX_GEN_*, payloads > 65535 bytes)")
 
 
+def _outside_contract(i: int, kind) -> ContractError:
+    """The slot value of a line the front end's kernel does not take (SDX_LS_UNSUPPORTED), ``kind`` its line kind."""
+    return ContractError(f"line {i} is outside the device contract of the front end "
+                         f"(kind {_KIND_NAME.get(int(kind), '?')})")
+
+
 def pack_lines(lines: Sequence[Union[str, bytes]], copy: bool = True):
     """Concatenate lines into (data uint8, offsets int64[n+1]); per-line ContractError where a line
     cannot be represented (returned in ``bad``; such lines are replaced by an empty line).
@@ -464,8 +470,7 @@ class SignalParser:
                 continue
             st = status_l[i]
             if st == runtime.LS_UNSUPPORTED:
-                out.append(ContractError(f"line {i} is outside the device contract of the front end "
-                                         f"(kind {_KIND_NAME.get(kind_l[i], '?')})"))
+                out.append(_outside_contract(i, kind_l[i]))
                 continue
             name = _KIND_NAME.get(kind_l[i])
             if st == runtime.LS_GENERAL:
@@ -766,6 +771,81 @@ class SignalParser:
             kept.append((kind, out, json_cap))
         return kept
 
+    def _record_passes(self, n: int, kept, lo, profiles=None, sources=None, dispatch=None):
+        """_demodulate_kept's outputs through the record passes, right behind the launches: sdx_filter_records
+        (``profiles``, ``sources``), then sdx_dispatch_records (``dispatch``).  Every line keeps the records the pass
+        keeps, compacted in line order; everything behind reads the rewritten outputs (they share the launches' heaps)."""
+        eng = self.protocols._ensure()
+
+        def through(kept, alloc, run):
+            bufs = alloc(n, [o for _, o, _ in kept])
+            outs = run([eng.json_in(kind, o, lo, n) for kind, o, _ in kept], bufs)
+            return [(kind, x, json_cap) for (kind, _, json_cap), x in zip(kept, outs)]
+
+        if kept and profiles is not None:
+            kept = through(kept, eng.alloc_profiles, lambda ins, bufs: eng.filter_records(
+                profiles, ins, n, bufs, source=None if sources is None else eng.torch.from_numpy(
+                    np.ascontiguousarray(sources, np.int32)).to(eng.dev)))
+        if kept and dispatch is not None:
+            kept = through(kept, eng.alloc_dispatch, lambda ins, bufs: eng.dispatch_records(dispatch, ins, n, bufs))
+        return kept
+
+    @staticmethod
+    def _pass_kw(rows, profiles=None, sources=None, dispatch=None) -> dict:
+        """The profile and dispatch keywords of a parse_lines* call over the lines ``rows`` of this batch."""
+        kw = {} if dispatch is None else {"dispatch": dispatch}
+        if profiles is not None:
+            kw.update(profiles=profiles, sources=None if sources is None else [int(sources[i]) for i in rows])
+        return kw
+
+    def _host_rows(self, lines, lb: LineBatch, bad: dict, host_rows: List[int], slots: list, put, **passes):
+        """The rows the host resolves: the general-path lines (rare), ``host_rows``, and the unsupported MU/MS lines
+        with them -- parse_lines resolves the ones whose P# values need the exact float() (sdx_lines_exact); the
+        others come back as ContractError.  ``put(i, g)`` takes line i's parse_lines value (``passes``: its profile
+        and dispatch keywords); then ``slots`` gets the ``bad`` values and the ContractErrors.  -> the line kinds."""
+        n = len(lines)
+        status = lb.status[:n].cpu().numpy()
+        kinds = lb.kind[:n].cpu().numpy()
+        exact = (status == runtime.LS_UNSUPPORTED) & ((kinds == runtime.LINE_MU) | (kinds == runtime.LINE_MS))
+        grows = [int(i) for i in np.nonzero((status == runtime.LS_GENERAL) | exact)[0] if int(i) not in bad] + host_rows
+        resolved = set()
+        if grows:
+            for i, g in zip(grows, self.parse_lines([lines[i] for i in grows], **self._pass_kw(grows, **passes))):
+                if exact[i] and not isinstance(g, ContractError):
+                    resolved.add(i)   # else still unsupported: reported below, under its index in this batch
+                put(i, g)
+        for i in range(n):
+            if i in bad:
+                slots[i] = bad[i]
+            elif int(status[i]) == runtime.LS_UNSUPPORTED and i not in resolved:
+                slots[i] = _outside_contract(i, kinds[i])
+        return kinds
+
+    def _reconcile_repeats(self, slots: list, kinds, rpass, rbufs, rep, has_text, host_keys: dict, times, rsources,
+                           empty, first, one) -> None:
+        """The device's repeat mask ``rep`` made exact where host-resolved rows stand in a run, and ``slots`` with
+        it; the mask is left in last_repeat_mask.  ``empty``: a dropped line's slot value; ``first(x)``: the first
+        text of the slot value x, None where it has none; ``one(i)``: line i's slot value computed on its own."""
+        import copy
+        from .repeats import apply_mask, text_key
+        fetched = {}
+        key = lambda i, x: None if first(x) is None else text_key(_KIND_NAME[int(kinds[i])], first(x))   # noqa: E731
+
+        def fetch_key(i):   # a flagged line whose run head the host does not know: the batch API
+            fetched[i] = one(i)
+            return key(i, fetched[i])
+
+        mask = rpass.exact_mask(rbufs, rep, has_text, lambda i: key(i, slots[i]), host_keys, fetch=fetch_key, times=times,
+                                sources=rsources)
+
+        def drop(i):         # a host-resolved repeat, or a repeat of a host-resolved line
+            slots[i] = copy.copy(empty)
+
+        def republish(i):    # the device skipped it, but its predecessor was a host row
+            slots[i] = fetched[i] if i in fetched else one(i)
+        apply_mask(mask, rep, host_keys, drop, republish)
+        self.last_repeat_mask = mask
+
     def _texts(self, lines, lb: LineBatch, bad: dict, nbytes: int, collapse: bool = False, times=None,
                window_us: Optional[int] = None, sources=None, routes=None, drop_unrouted: bool = False,
                match_any: bool = False, profiles=None):
@@ -813,21 +893,14 @@ class SignalParser:
         route = np.full(n, -1, np.int16)   # the lines' routes (routes)
         pick = np.zeros(n, np.uint16)      # the lines' picked records (match_any)
         if collapse:
-            from .repeats import RepeatPass, apply_mask, count_sources, objects_key, text_key
+            from .repeats import RepeatPass, count_sources, objects_key
             rpass = RepeatPass(eng, window_us, None if sources is None else count_sources(sources))
             rbufs = None
         if collapse or routes is not None or profiles is not None:
             # every kind's launch first (their outputs stay on the device), then ONE sdx_mark_repeats over
             # them, then the serialiser with the mask: a repeat is never turned into text
             kept = self._demodulate_kept(n, pb, jobs, elig, host_rows)
-            if kept and profiles is not None:
-                # right behind the launches: every line keeps the records its source's profile enables, compacted
-                # in line order; everything below reads the filtered outputs (they share the launches' heaps)
-                pbufs = eng.alloc_profiles(n, [out for _, out, _ in kept])
-                d_src = None if sources is None else eng.torch.from_numpy(np.ascontiguousarray(sources, np.int32)).to(eng.dev)
-                fouts = eng.filter_records(profiles, [eng.json_in(kind, out, lo, n) for kind, out, _ in kept], n, pbufs,
-                                           source=d_src)
-                kept = [(kind, fo, json_cap) for (kind, _, json_cap), fo in zip(kept, fouts)]
+            kept = self._record_passes(n, kept, lo, profiles, sources)
             if kept:   # a fresh stream of lines per call; nothing is read back but the mask (and the sources' table)
                 ins = [eng.json_in(kind, out, lo, n) for kind, out, _ in kept]
                 skip = None
@@ -887,66 +960,34 @@ class SignalParser:
             else:
                 raise RuntimeError("result / JSON capacity overflow persists")
             take_texts(jo, c2[0])
-        status = lb.status[:n].cpu().numpy()
-        kinds = lb.kind[:n].cpu().numpy()
-        # ... and the unsupported MU/MS lines with them: parse_lines resolves the ones whose P# values
-        # need the exact float() (sdx_lines_exact); the others come back as ContractError
-        exact = (status == runtime.LS_UNSUPPORTED) & ((kinds == runtime.LINE_MU) | (kinds == runtime.LINE_MS))
-        grows = [int(i) for i in np.nonzero((status == runtime.LS_GENERAL) | exact)[0] if int(i) not in bad] + host_rows
-        resolved = set()
         has_text = np.fromiter((x is not None for x in texts), bool, n) if collapse else None
         host_keys = {}   # collapse: the host-resolved rows' keys (None: no result)
-        if grows:  # general-path lines (rare): their objects through parse_lines, the text as _message_to_json
-            gkw = {} if profiles is None else {"profiles": profiles,
-                                               "sources": None if sources is None else [int(sources[i]) for i in grows]}
-            for i, g in zip(grows, self.parse_lines([lines[i] for i in grows], **gkw)):
-                if match_any and isinstance(g, list) and g:   # the published message is the picked one
-                    pick[i], route[i], _ = routes.pick([m.payload for m in g])
-                    g = g[int(pick[i]): int(pick[i]) + 1]
-                if collapse:
-                    host_keys[i] = objects_key(g)
-                if exact[i]:
-                    if isinstance(g, ContractError):
-                        continue   # still unsupported: reported below, under its index in this batch
-                    resolved.add(i)
-                if isinstance(g, BaseException):
-                    texts[i] = g
-                elif g:
-                    texts[i] = json.dumps({"protocol_id": g[0].protocol_id, "payload": g[0].payload,
-                                           "metadata": g[0].metadata}, indent=4)
-                    if routes is not None and not match_any:   # a host-resolved line: the same tables, walked on the host
-                        route[i] = routes.match(g[0].payload)[0]
-        for i in range(n):
-            if i in bad:
-                texts[i] = bad[i]
-            elif int(status[i]) == runtime.LS_UNSUPPORTED and i not in resolved:
-                texts[i] = ContractError(f"line {i} is outside the device contract of the front end "
-                                         f"(kind {_KIND_NAME.get(int(kinds[i]), '?')})")
-        if collapse:
-            fetched = {}
 
+        def put(i, g):   # a host-resolved line: its objects from parse_lines, the text as _message_to_json
+            if match_any and isinstance(g, list) and g:   # the published message is the picked one
+                pick[i], route[i], _ = routes.pick([m.payload for m in g])
+                g = g[int(pick[i]): int(pick[i]) + 1]
+            if collapse:
+                host_keys[i] = objects_key(g)
+            if isinstance(g, BaseException):
+                texts[i] = g
+            elif g:
+                texts[i] = json.dumps({"protocol_id": g[0].protocol_id, "payload": g[0].payload,
+                                       "metadata": g[0].metadata}, indent=4)
+                if routes is not None and not match_any:   # the same tables, walked on the host
+                    route[i] = routes.match(g[0].payload)[0]
+
+        kinds = self._host_rows(lines, lb, bad, host_rows, texts, put, profiles=profiles, sources=sources)
+        if collapse:
             def one_text(i):    # the line's published text on its own (match_any: the picked message's)
-                pkw = {} if profiles is None else {"profiles": profiles, "sources": None if sources is None else [int(sources[i])]}
+                pkw = self._pass_kw([i], profiles, sources)
                 if not match_any:
                     return self.parse_lines_json([lines[i]], **pkw)[0]
                 x = self.parse_lines_routed([lines[i]], routes, route_match="any", **pkw)[0]
                 return x[1] if isinstance(x, tuple) else x
 
-            def fetch_key(i):   # a flagged line whose run head the host does not know: the batch API
-                fetched[i] = one_text(i)
-                return text_key(_KIND_NAME[int(kinds[i])], fetched[i]) if isinstance(fetched[i], str) else None
-
-            dev_key_of = lambda i: text_key(_KIND_NAME[int(kinds[i])], texts[i])   # noqa: E731
-            mask = rpass.exact_mask(rbufs, rep, has_text, dev_key_of, host_keys, fetch=fetch_key, times=times,
-                                    sources=rsources)
-
-            def drop(i):         # a host-resolved repeat, or a repeat of a host-resolved line
-                texts[i] = None
-
-            def republish(i):    # the device skipped it, but its predecessor was a host row
-                texts[i] = fetched[i] if i in fetched else one_text(i)
-            apply_mask(mask, rep, host_keys, drop, republish)
-            self.last_repeat_mask = mask
+            self._reconcile_repeats(texts, kinds, rpass, rbufs, rep, has_text, host_keys, times, rsources, None,
+                                    lambda x: x if isinstance(x, str) else None, one_text)
         if routes is not None:
             self.last_routes = route
             self.last_picks = pick if match_any else None
@@ -1013,20 +1054,12 @@ class SignalParser:
         out: List[Any] = [[] for _ in range(n)]
         host_rows: List[int] = []   # lines whose texts are built from parse_lines' objects (general paths)
         kept = self._demodulate_kept(n, pb, jobs, self._mn_elig(profiles), host_rows)
+        kept = self._record_passes(n, kept, lo, profiles, sources, dispatch)
         ins_of = lambda ks: [eng.json_in(kind, o, lo, n) for kind, o, _ in ks]   # noqa: E731
-        if kept and profiles is not None:
-            pbufs = eng.alloc_profiles(n, [o for _, o, _ in kept])
-            d_src = None if sources is None else eng.torch.from_numpy(np.ascontiguousarray(sources, np.int32)).to(eng.dev)
-            fouts = eng.filter_records(profiles, ins_of(kept), n, pbufs, source=d_src)
-            kept = [(kind, fo, json_cap) for (kind, _, json_cap), fo in zip(kept, fouts)]
-        if kept and dispatch is not None:
-            dbufs = eng.alloc_dispatch(n, [o for _, o, _ in kept])
-            douts = eng.dispatch_records(dispatch, ins_of(kept), n, dbufs)
-            kept = [(kind, do, json_cap) for (kind, _, json_cap), do in zip(kept, douts)]
         rep = np.zeros(n, np.uint8)
         rbufs = None
         if collapse:
-            from .repeats import RepeatPass, apply_mask, count_sources, objects_key, text_key
+            from .repeats import RepeatPass, count_sources, objects_key
             rpass = RepeatPass(eng, window_us, None if sources is None else count_sources(sources))
         if kept:
             skip = None
@@ -1038,57 +1071,21 @@ class SignalParser:
                 self._take_texts_all(out, n, kind, o, lo, 2 * json_cap, skip)
             if collapse:
                 rep = rbufs.mask[:n].cpu().numpy()
-        status = lb.status[:n].cpu().numpy()
-        kinds = lb.kind[:n].cpu().numpy()
-        exact = (status == runtime.LS_UNSUPPORTED) & ((kinds == runtime.LINE_MU) | (kinds == runtime.LINE_MS))
-        grows = [int(i) for i in np.nonzero((status == runtime.LS_GENERAL) | exact)[0] if int(i) not in bad] + host_rows
-        resolved = set()
         has_text = np.fromiter((bool(x) for x in out), bool, n) if collapse else None
         host_keys = {}   # collapse: the host-resolved rows' keys (None: no result)
+        passes = {"profiles": profiles, "sources": sources, "dispatch": dispatch}
 
-        def kw_for(rows):
-            kw = {} if dispatch is None else {"dispatch": dispatch}
-            if profiles is not None:
-                kw.update(profiles=profiles, sources=None if sources is None else [int(sources[i]) for i in rows])
-            return kw
+        def put(i, g):   # a host-resolved line: its objects from parse_lines, every message's text on the host
+            if collapse:
+                host_keys[i] = objects_key(g)
+            out[i] = g if isinstance(g, BaseException) else [
+                json.dumps({"protocol_id": m.protocol_id, "payload": m.payload, "metadata": m.metadata}, indent=4) for m in g]
 
-        if grows:  # host-resolved lines (rare): their objects through parse_lines, every message's text on the host
-            for i, g in zip(grows, self.parse_lines([lines[i] for i in grows], **kw_for(grows))):
-                if collapse:
-                    host_keys[i] = objects_key(g)
-                if exact[i]:
-                    if isinstance(g, ContractError):
-                        continue   # still unsupported: reported below, under its index in this batch
-                    resolved.add(i)
-                out[i] = g if isinstance(g, BaseException) else [
-                    json.dumps({"protocol_id": m.protocol_id, "payload": m.payload, "metadata": m.metadata}, indent=4) for m in g]
-        for i in range(n):
-            if i in bad:
-                out[i] = bad[i]
-            elif int(status[i]) == runtime.LS_UNSUPPORTED and i not in resolved:
-                out[i] = ContractError(f"line {i} is outside the device contract of the front end "
-                                       f"(kind {_KIND_NAME.get(int(kinds[i]), '?')})")
+        kinds = self._host_rows(lines, lb, bad, host_rows, out, put, **passes)
         if collapse:
-            fetched = {}
-
-            def one_list(i):    # the line's texts on their own
-                return self.parse_lines_json_all([lines[i]], **kw_for([i]))[0]
-
-            def fetch_key(i):   # a flagged line whose run head the host does not know: the batch API
-                fetched[i] = one_list(i)
-                return text_key(_KIND_NAME[int(kinds[i])], fetched[i][0]) if isinstance(fetched[i], list) and fetched[i] else None
-
-            dev_key_of = lambda i: text_key(_KIND_NAME[int(kinds[i])], out[i][0])   # noqa: E731
-            mask = rpass.exact_mask(rbufs, rep, has_text, dev_key_of, host_keys, fetch=fetch_key, times=times,
-                                    sources=rsources)
-
-            def drop(i):         # a host-resolved repeat, or a repeat of a host-resolved line
-                out[i] = []
-
-            def republish(i):    # the device skipped it, but its predecessor was a host row
-                out[i] = fetched[i] if i in fetched else one_list(i)
-            apply_mask(mask, rep, host_keys, drop, republish)
-            self.last_repeat_mask = mask
+            self._reconcile_repeats(out, kinds, rpass, rbufs, rep, has_text, host_keys, times, rsources, [],
+                                    lambda x: x[0] if isinstance(x, list) and x else None,
+                                    lambda i: self.parse_lines_json_all([lines[i]], **self._pass_kw([i], **passes))[0])
         return out
 
     def _take_texts_all(self, out: list, n: int, kind, o, lo, json_cap: int, skip) -> None:

@@ -1015,47 +1015,62 @@ class Engine:
         compacted in line order into ``bufs`` (alloc_profiles').  ``source``: a device int32 tensor, one id per line;
         None = every line is source 0.  ``rec_caps``: the record capacities to declare (default: the buffers').
         Returns bufs["outs"]: filtered outs shaped like alloc_out's, sharing the launches' heaps."""
-        n = int(n)
         if not isinstance(table, DeviceProfileTable):
             table = self.profile_table(table)
+        return self._compact("filter_records", self.lib.sdx_filter_records, self.lib.sdx_profile_scratch_bytes,
+                             table.handle, json_ins, n, bufs, stream, rec_caps, source)
+
+    def _compact(self, name, entry, scratch_bytes, arg, json_ins, n, bufs, stream, rec_caps, source=False):
+        """What filter_records and dispatch_records share: ``entry`` (after the bank: ``arg``, its table or rules)
+        over ``json_ins`` into ``bufs``; ``source``: the entry's per-line source ids, False where it takes none."""
+        n = int(n)
         outs = bufs["outs"]
         if len(outs) != len(json_ins):
-            raise ValueError("filter_records: one output per kind")
+            raise ValueError(name + ": one output per kind")
         k = max(len(outs), 1)
         caps = [o["rec_cap"] for o in outs] if rec_caps is None else [int(c) for c in rec_caps]
         for o, c in zip(outs, caps):
             if o["rec"].numel() < c * RES_DT.itemsize:
-                raise ValueError("filter_records: a record buffer is smaller than its declared capacity")
+                raise ValueError(name + ": a record buffer is smaller than its declared capacity")
         darr = (c_void_p * k)(*[_ptr(o["desc"]) for o in outs])
         rarr = (c_void_p * k)(*[_ptr(o["rec"]) for o in outs])
         carr = (c_void_p * k)(*[_ptr(o["cursor"]) for o in outs])
         caparr = (ctypes.c_uint32 * k)(*caps)
-        need = int(self.lib.sdx_profile_scratch_bytes(k, n)) if 1 <= len(outs) <= 4 and n >= 0 else 0
-        self._mark("filter_records",
-                   lambda bank, arr, k_, n_, *a: self.lib.sdx_filter_records(bank, table.handle, arr, k_, n_, *a),
-                   json_ins, n, [(source, 4 * n), (bufs["scratch"], need)] + [(o["desc"], 8 * n) for o in outs],
-                   (_ptr(source), darr, rarr, caparr, carr, _ptr(bufs["scratch"])), stream)
+        need = int(scratch_bytes(k, n)) if 1 <= len(outs) <= 4 and n >= 0 else 0
+        src = [] if source is False else [(source, 4 * n)]
+        self._mark(name, lambda bank, arr, k_, n_, *a: entry(bank, arg, arr, k_, n_, *a),
+                   json_ins, n, src + [(bufs["scratch"], need)] + [(o["desc"], 8 * n) for o in outs],
+                   (*[_ptr(t_) for t_, _ in src], darr, rarr, caparr, carr, _ptr(bufs["scratch"])), stream)
         return outs
 
     def filter_fetched(self, table, res: dict, n: int, sources=None) -> dict:
         """filter_records for results already on the host (run()'s): ``res`` maps "MU" / "MS" / "MC" / "MN" to
         (desc, rec, heap) as run() returns them; their descriptors and records go up again, through the pass, and
         come back filtered (the heaps stay: payload offsets are unchanged).  ``sources``: int32[n] or None."""
+        src = None if sources is None else self.torch.from_numpy(np.ascontiguousarray(sources, np.int32)).to(self.dev)
+        return self._fetched(res, n, False, self.alloc_profiles,
+                             lambda ins, bufs: self.filter_records(table, ins, n, bufs, source=src))
+
+    def _fetched(self, res: dict, n: int, heap_up: bool, alloc, run) -> dict:
+        """What filter_fetched and dispatch_fetched share: descriptors and records (``heap_up``: and heaps) up,
+        ``run(json_ins, alloc(n, outs))``, descriptors and records back."""
         t = self.torch
         names = [k for k in ("MU", "MS", "MC", "MN") if k in res]
         up = lambda a: t.from_numpy(np.frombuffer(a.tobytes(), np.uint8).copy()).to(self.dev)   # noqa: E731
         outs, ins = [], []
         for name in names:
-            desc, rec, _ = res[name]
+            desc, rec, heap = res[name]
             o = {"desc": up(desc) if len(desc) else t.zeros(8, dtype=t.uint8, device=self.dev),
                  "rec": up(rec) if len(rec) else t.zeros(RES_DT.itemsize, dtype=t.uint8, device=self.dev),
-                 "cursor": t.tensor([len(rec), 0, 0, 0], dtype=t.int32, device=self.dev), "rec_cap": len(rec), "heap_cap": 0, "n": n}
-            o["heap"] = o["desc"]    # never read by the pass
+                 "cursor": t.tensor([len(rec), 0, 0, 0], dtype=t.int32, device=self.dev), "rec_cap": len(rec),
+                 "heap_cap": len(heap) if heap_up else 0, "n": n}
+            if heap_up:
+                o["heap"] = up(heap) if len(heap) else t.zeros(16, dtype=t.uint8, device=self.dev)
+            else:
+                o["heap"] = o["desc"]    # never read by the pass
             outs.append(o)
             ins.append(self.json_in(("MU", "MS", "MC", "MN").index(name), o, {"meta": o["desc"]}, n))
-        bufs = self.alloc_profiles(n, outs)
-        src = None if sources is None else t.from_numpy(np.ascontiguousarray(sources, np.int32)).to(self.dev)
-        f = self.filter_records(table, ins, n, bufs, source=src)
+        f = run(ins, alloc(n, outs))
         out = dict(res)
         for name, o in zip(names, f):
             total = int(o["cursor"][0].item())
@@ -1065,12 +1080,9 @@ class Engine:
 
     # -- dispatch rules (sdx_dispatch_records) ----------------------------------------
     def alloc_dispatch(self, n: int, outs):
-        """The buffers of dispatch_records for chunks of up to n lines whose launches write ``outs``: as
-        alloc_profiles', with sdx_dispatch_scratch_bytes of scratch."""
-        bufs = self.alloc_profiles(n, outs)
-        size = int(self.lib.sdx_dispatch_scratch_bytes(max(len(outs), 1), max(int(n), 1)))
-        bufs["scratch"] = self.torch.empty(size, dtype=self.torch.uint8, device=self.dev)
-        return bufs
+        """The buffers of dispatch_records for chunks of up to n lines whose launches write ``outs``: 
+        alloc_profiles' (sdx_dispatch_scratch_bytes and sdx_profile_scratch_bytes are one formula)."""
+        return self.alloc_profiles(n, outs)
 
     def dispatch_records(self, rules, json_ins, n: int, bufs, stream=None, rec_caps=None):
         """sdx_dispatch_records on ``stream`` (default: the current one; no host sync): the launch outputs behind
@@ -1078,56 +1090,20 @@ class Engine:
         (``rules``: a dispatch.DispatchRules, True for the defaults, or a filled SdxDispatchRules), compacted in line
         order into ``bufs`` (alloc_dispatch's).  ``rec_caps``: the record capacities to declare (default: the
         buffers').  Returns bufs["outs"]: reduced outs shaped like alloc_out's, sharing the launches' heaps."""
-        n = int(n)
         if not isinstance(rules, SdxDispatchRules):
             from .dispatch import as_rules
             rules = as_rules(rules)
             if rules is None:
                 raise ValueError("dispatch_records: no rules")
             rules = rules.struct(self.bank)
-        outs = bufs["outs"]
-        if len(outs) != len(json_ins):
-            raise ValueError("dispatch_records: one output per kind")
-        k = max(len(outs), 1)
-        caps = [o["rec_cap"] for o in outs] if rec_caps is None else [int(c) for c in rec_caps]
-        for o, c in zip(outs, caps):
-            if o["rec"].numel() < c * RES_DT.itemsize:
-                raise ValueError("dispatch_records: a record buffer is smaller than its declared capacity")
-        darr = (c_void_p * k)(*[_ptr(o["desc"]) for o in outs])
-        rarr = (c_void_p * k)(*[_ptr(o["rec"]) for o in outs])
-        carr = (c_void_p * k)(*[_ptr(o["cursor"]) for o in outs])
-        caparr = (ctypes.c_uint32 * k)(*caps)
-        need = int(self.lib.sdx_dispatch_scratch_bytes(k, n)) if 1 <= len(outs) <= 4 and n >= 0 else 0
-        self._mark("dispatch_records",
-                   lambda bank, arr, k_, n_, *a: self.lib.sdx_dispatch_records(bank, ctypes.byref(rules), arr, k_, n_, *a),
-                   json_ins, n, [(bufs["scratch"], need)] + [(o["desc"], 8 * n) for o in outs],
-                   (darr, rarr, caparr, carr, _ptr(bufs["scratch"])), stream)
-        return outs
+        return self._compact("dispatch_records", self.lib.sdx_dispatch_records, self.lib.sdx_dispatch_scratch_bytes,
+                             ctypes.byref(rules), json_ins, n, bufs, stream, rec_caps)
 
     def dispatch_fetched(self, rules, res: dict, n: int) -> dict:
         """dispatch_records for results already on the host (run()'s), as filter_fetched -- but the heaps go up too:
         this pass reads payloads.  The heaps themselves stay as they are (payload offsets are unchanged)."""
-        t = self.torch
-        names = [k for k in ("MU", "MS", "MC", "MN") if k in res]
-        up = lambda a: t.from_numpy(np.frombuffer(a.tobytes(), np.uint8).copy()).to(self.dev)   # noqa: E731
-        outs, ins = [], []
-        for name in names:
-            desc, rec, heap = res[name]
-            o = {"desc": up(desc) if len(desc) else t.zeros(8, dtype=t.uint8, device=self.dev),
-                 "rec": up(rec) if len(rec) else t.zeros(RES_DT.itemsize, dtype=t.uint8, device=self.dev),
-                 "heap": up(heap) if len(heap) else t.zeros(16, dtype=t.uint8, device=self.dev),
-                 "cursor": t.tensor([len(rec), 0, 0, 0], dtype=t.int32, device=self.dev), "rec_cap": len(rec),
-                 "heap_cap": len(heap), "n": n}
-            outs.append(o)
-            ins.append(self.json_in(("MU", "MS", "MC", "MN").index(name), o, {"meta": o["desc"]}, n))
-        bufs = self.alloc_dispatch(n, outs)
-        f = self.dispatch_records(rules, ins, n, bufs)
-        out = dict(res)
-        for name, o in zip(names, f):
-            total = int(o["cursor"][0].item())
-            out[name] = (o["desc"][: n * DESC_DT.itemsize].cpu().numpy().view(DESC_DT).copy(),
-                         o["rec"][: total * RES_DT.itemsize].cpu().numpy().view(RES_DT).copy(), res[name][2])
-        return out
+        return self._fetched(res, n, True, self.alloc_dispatch,
+                             lambda ins, bufs: self.dispatch_records(rules, ins, n, bufs))
 
     def alloc_json(self, items: int, cap: int):
         t, d = self.torch, self.dev

@@ -135,9 +135,10 @@ class Chunk:
             res.append((desc, stored, cur))
         return res
 
-    def run(self, rules, caps=None, guard=4):
-        """The pass over the chunk.  Outputs are pre-filled with 9s; the record arrays own ``guard`` records of 0xA5
-        behind the declared capacity.  -> per kind (descriptors, the whole record buffer as bytes, cursor), the outs."""
+    def run(self, rules, caps=None, guard=4, call=None):
+        """The pass over the chunk (``call``: another pass with dispatch_records' arguments).  Outputs are pre-filled
+        with 9s; the record arrays own ``guard`` records of 0xA5 behind the declared capacity.  -> per kind
+        (descriptors, the whole record buffer as bytes, cursor), the outs."""
         from pysignalduino_amd import runtime
         eng, n, t = self.eng, self.n, self.eng.torch
         caps = [o["rec_cap"] for o in self.outs] if caps is None else list(caps)
@@ -149,7 +150,7 @@ class Chunk:
             o["desc"].fill_(9)
             o["cursor"].view(t.uint8).fill_(9)
         bufs["scratch"].fill_(0xEE)
-        outs = eng.dispatch_records(rules, self.ins, n, bufs, rec_caps=caps)
+        outs = (call or eng.dispatch_records)(rules, self.ins, n, bufs, rec_caps=caps)
         t.cuda.synchronize()
         got = [(o["desc"][: 8 * n].cpu().numpy().view(runtime.DESC_DT), o["rec"].cpu().numpy().tobytes(),
                 o["cursor"].cpu().numpy().view(np.uint32)) for o in outs]
@@ -390,6 +391,32 @@ def test_capacity_contract(eng, default_rules):
                 assert n_ovf == 1                                                    # the last line that keeps something
             fit = d[(d["status"] == OK) & (d["n_rec"] > 0)]
             assert all(int(f["rec_begin"]) + int(f["n_rec"]) <= caps[x] for f in fit)
+
+
+# ---- one skeleton, two policies -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("short", [0, 1])
+@pytest.mark.parametrize("n", [1, 255, 256, 257])
+def test_no_rule_equals_the_profile_pass_with_every_class_enabled(eng, n, short):
+    """sdx_dispatch_records with no rule on and sdx_filter_records with every class enabled both keep every record
+    of every OK line, through the same count -> scan -> write (csrc/sdx_compact.h): descriptors, whole record
+    buffers (so the records up to cursor[0], and the 9s and guards behind them) and the four cursor words are the
+    same bytes.  ``short``: every kind's capacity is one record short of its demand, so both passes meet a list
+    that does not fit."""
+    from pysignalduino_amd import runtime
+    from test_profiles import ALL, pack_table
+    lines = mixed_lines(n, seed=40 + n) if n > 1 else [[(0, [(5, b"70"), (5, b"70"), (10, b"A0F3")])]]
+    c = Chunk(eng, lines, kinds=(0, 1, 2, 3))
+    demand = [int(d["n_rec"][d["status"] == OK].sum()) for d in c.desc]
+    assert demand[0] > 0
+    caps = [max(d - 1, 0) for d in demand] if short else None
+    got, _, _, _ = c.check(mk_rules(cap=0, drop=0), caps=caps)
+    table = runtime.DeviceProfileTable(eng, None, blob=pack_table([ALL], [0]))
+    same, _, _, _ = c.run(None, caps, call=lambda _, ins, n_, bufs, rec_caps: eng.filter_records(table, ins, n_, bufs,
+                                                                                                rec_caps=rec_caps))
+    for x, ((dd, dr, dc), (fd, fr, fc)) in enumerate(zip(got, same)):
+        assert dc.tolist() == fc.tolist() and dc[0] == demand[x], (x, dc, fc)
+        assert dd.tobytes() == fd.tobytes() and dr == fr, x
+        assert bool((dd["status"][c.desc[x]["status"] == OK] == OVF_OUT).any()) == bool(short and demand[x])
 
 
 # ---- SDX_EINVAL ---------------------------------------------------------------------------------------------------
