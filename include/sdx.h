@@ -667,6 +667,36 @@ int sdx_dispatch_records(const sdx_bank* bank, const sdx_dispatch_rules* rules, 
                          int32_t n, sdx_desc* const* desc_out, sdx_result* const* rec_out, const uint32_t* rec_cap,
                          uint32_t* const* cursor_out, void* scratch_dev, void* hip_stream);
 
+/* ---- every message of a line in ONE chunk result ------------------------------------
+ * The launches of a chunk keep one record array per kind; a result that carries every message of every line
+ * needs one place per record that all kinds share.  sdx_index_records gives it: for the chunk's n lines, in
+ * line order, COUNT(g) = the n_rec of line g's descriptor in the one kind where that descriptor is SDX_ST_OK
+ * with n_rec > 0 (lines of other classes keep a zeroed descriptor there; the kinds' terms are summed), and 0
+ * when skip_dev is non-NULL and skip_dev[g] != 0 or the status is RAISED / OVF_OUT / OVF_TILE / ABSENT.
+ * first_dev[g] = the exclusive prefix of the counts, first_dev[n] = their total (below 2^32: the caller's record
+ * capacities bound it): every entry of first_dev[0, n] is written, nothing beyond it; n = 0 writes
+ * first_dev[0] = 0.  kinds[0..k): as sdx_mark_repeats takes them (k = 1..4, no kind twice, and its checks); only
+ * kind, desc_dev and n are read.  scratch_dev: sdx_index_scratch_bytes(n) bytes, contents free.  Three launches
+ * (count, scan, add; n = 0: the scan alone) on the caller's stream; no allocation, no synchronisation, no global
+ * atomics, no spinning, the same bytes every run.  SDX_EINVAL (nothing launched): what sdx_mark_repeats refuses
+ * of kinds / k / n, a null first_dev, a null scratch_dev with n > 0, a first_dev or scratch_dev that is not
+ * 4-byte aligned.
+ * sdx_serialize_json_lines is sdx_serialize_json with first_only = 0 (in->first_only must be 0) that writes a
+ * record's offset and length at its CHUNK record index: lane = record g < min(cursor[0], in->rec_max) of this
+ * kind, m = rec[g].msg, d = desc[m], j = g - d.rec_begin.  The record gets a text iff d.status == SDX_ST_OK,
+ * j < d.n_rec and j < first_dev[m + 1] - first_dev[m] (no record of a skipped line; none that no OK descriptor
+ * covers, as the stale records of an overflowed line); it is written at c = first_dev[m] + j: out->off_dev[c],
+ * out->len_dev[c], with rec_max the capacity of those two arrays.  c >= rec_max: nothing is stored and
+ * out->cursor_dev[1] |= 1, the flag of a text-buffer overflow, on which len[c] = 0 as in sdx_serialize_json.  All
+ * kinds of a chunk share one json_dev / off_dev / len_dev / cursor_dev: every entry of off / len in
+ * [0, min(first_dev[n], rec_max)) is written by exactly one lane of one kind's call, none at or beyond rec_max,
+ * no byte at or beyond json_cap. */
+size_t sdx_index_scratch_bytes(int32_t n);
+int sdx_index_records(const sdx_json_in* kinds, int32_t k, int32_t n, const uint8_t* skip_dev,
+                      uint32_t* first_dev /* [n + 1] */, void* scratch_dev, void* hip_stream);
+int sdx_serialize_json_lines(const sdx_bank* bank, const sdx_json_in* in, const sdx_json_out* out,
+                             const uint32_t* first_dev, uint32_t rec_max, void* hip_stream);
+
 /* ---- unit-level entry ------------------------------------------------------------------------
  * The reference's helper methods that its own unit tests call on SDProtocols, evaluated on n
  * independent inputs in one launch (lane = item), with the device code the demodulation kernels

@@ -16,6 +16,7 @@ SRCS = [os.path.join(HERE, "csrc", "sdx_kernels.hip"),   # demodulation kernels 
         os.path.join(HERE, "csrc", "sdx_route.hip"),     # payload routes (sdx_route_lines)
         os.path.join(HERE, "csrc", "sdx_profile.hip"),   # receiver profiles (sdx_filter_records)
         os.path.join(HERE, "csrc", "sdx_dispatch.hip"),  # dispatch rules (sdx_dispatch_records)
+        os.path.join(HERE, "csrc", "sdx_index.hip"),     # line -> record-range index (sdx_index_records)
         os.path.join(HERE, "csrc", "sdx_units.hip"),     # unit-level helpers (sdx_units)
         os.path.join(HERE, "csrc", "sdx_exchange.hip"),  # multi-GPU exchange packing (sdx_exchange_pack)
         os.path.join(HERE, "csrc", "sdx_group.hip"),     # MU/MS message grouping (k_sig + radix sort)

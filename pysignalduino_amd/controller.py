@@ -51,6 +51,14 @@ matches (its text is never built) -- its line keeps its ``_handle_as_command_res
 starts and breaks runs of repeats as before.  The defaults publish exactly as without routes.
 ``route_match="any"``: of a line that demodulates to several messages, the first one that
 some route matches is the telegram -- its text is published, to its client's topic with ``route_topics``.
+
+``publish="json_all"`` publishes EVERY message of a line, as FHEM dispatches them: per line its
+texts in order to ``<base_topic>/state/messages``, then the line's ``_handle_as_command_response`` turn under the
+same check.  ``rules`` (None: every message; True or a dispatch.DispatchRules) reduces every line's list by FHEM's
+dispatch rules first.  With ``stream=True`` the batches go through a ``json_all`` LineStream, with
+``stream=False`` through one ``parse_lines_json_all`` call per micro-batch (with ``collapse_repeats`` through a
+one-slot ``json_all`` LineStream drained per batch, which carries the run of repeats across micro-batches as the
+``json`` path does).  It takes no routes and, like ``publish="json"``, no ``message_callback``.
 """
 from __future__ import annotations
 
@@ -66,9 +74,17 @@ class BatchingParserTask:
                  logger: Optional[logging.Logger] = None, stream: bool = True, lag: int = 3,
                  collapse_repeats: bool = False, repeat_window: Optional[float] = None,
                  clock: Optional[Callable[[], int]] = None, routes=None, drop_unrouted: bool = False,
-                 route_topics: bool = False, route_match: str = "first", profiles=None):
-        if publish not in ("objects", "json"):
-            raise ValueError("publish must be 'objects' or 'json'")
+                 route_topics: bool = False, route_match: str = "first", profiles=None, rules=None):
+        if publish not in ("objects", "json", "json_all"):
+            raise ValueError("publish must be 'objects', 'json' or 'json_all'")
+        # every message of a line, reduced by the dispatch rules (§4o)
+        self.all = publish == "json_all"
+        from .dispatch import as_rules
+        self.rules = as_rules(rules)
+        if self.rules is not None and not self.all:
+            raise ValueError("rules need publish='json_all'")
+        if self.all and (routes is not None or drop_unrouted or route_topics or route_match != "first"):
+            raise ValueError("publish='json_all' takes no routes")
         # receiver profiles: a controller reads ONE receiver, so the table has one source
         from .profiles import as_profiles
         self.profiles = as_profiles(profiles)
@@ -87,8 +103,8 @@ class BatchingParserTask:
             raise ValueError("drop_unrouted / route_topics need routes")
         if self.routes is not None and publish != "json":
             raise ValueError("routes need publish='json'")
-        if publish == "json" and getattr(controller, "message_callback", None):
-            raise ValueError("publish='json' produces texts only; message_callback needs publish='objects'")
+        if publish != "objects" and getattr(controller, "message_callback", None):
+            raise ValueError(f"publish='{publish}' produces texts only; message_callback needs publish='objects'")
         if max_batch < 1:
             raise ValueError("max_batch must be >= 1")
         self.c = controller
@@ -98,7 +114,7 @@ class BatchingParserTask:
         self.logger = logger or getattr(controller, "logger", None) or logging.getLogger(__name__)
         self.batches = 0
         self.lines = 0
-        self.use_stream = stream and publish == "json"
+        self.use_stream = stream and publish != "objects"
         self.lag = lag
         self._stream = None
         self.collapse = bool(collapse_repeats)
@@ -240,7 +256,8 @@ class BatchingParserTask:
             for i, line in enumerate(lines):
                 res = res_at.get(i)
                 if res is not None:
-                    await self._publish_one(line, res)
+                    for x in (res if isinstance(res, list) else [res]):   # json_all: the line's texts in order
+                        await self._publish_one(line, x)
                 await c._handle_as_command_response(line)
             return
         lg = getattr(c, "logger", None)
@@ -266,13 +283,14 @@ class BatchingParserTask:
                 if not client:
                     log.warning("Attempted to publish without an active MQTT client.")
                 else:
-                    try:
-                        if isinstance(res, tuple):   # routes: (route, text)
-                            await client.publish(self._topic(pub.base_topic, res[0]), res[1])
-                        else:
-                            await client.publish(topic, res)
-                    except Exception:  # noqa: BLE001  (mqtt.py:271-272)
-                        log.error("Failed to publish message", exc_info=True)
+                    for x in (res if isinstance(res, list) else [res]):   # json_all: the line's texts in order
+                        try:
+                            if isinstance(x, tuple):   # routes: (route, text)
+                                await client.publish(self._topic(pub.base_topic, x[0]), x[1])
+                            else:
+                                await client.publish(topic, x)
+                        except Exception:  # noqa: BLE001  (mqtt.py:271-272)
+                            log.error("Failed to publish message", exc_info=True)
                     quiet = not (pend or dbg(D))
             if not quiet:
                 await handle(lines[i])
@@ -296,7 +314,10 @@ class BatchingParserTask:
             kw = {"collapse_repeats": True} if self.collapse else {}
             if self.window_us is not None:
                 kw["repeat_window"] = self.window_us / 1e6
-            self._stream = c.parser.stream(chunk_lines=self.max_batch, output="json", lag=self.lag, **kw, **self._route_kw())
+            if self.rules is not None:
+                kw["rules"] = self.rules
+            self._stream = c.parser.stream(chunk_lines=self.max_batch, output="json_all" if self.all else "json",
+                                           lag=self.lag, **kw, **self._route_kw())
         ls = self._stream
         # chunk id -> its lines: results are matched to their lines by id, never by position, so a
         # publication that fails part-way through a chunk cannot shift later chunks onto the wrong lines
@@ -310,7 +331,7 @@ class BatchingParserTask:
             while ready:
                 r = ready.popleft()
                 blines = pending.pop(r.id)
-                items = (self._routed_items(r) if self.routes is not None else
+                items = (r.items_all() if self.all else self._routed_items(r) if self.routes is not None else
                          r.items() if hasattr(r, "items") else [(i, t) for i, t in enumerate(r.texts()) if t is not None])
                 self.lines += len(blines)
                 await self._publish_items(blines, items)
@@ -381,6 +402,22 @@ class BatchingParserTask:
             self._last_key = k
         return results
 
+    def _parse_all(self, lines: List[Any], times: Optional[List[int]] = None) -> List[Any]:
+        """publish='json_all' without the pipelined stream: one micro-batch through parse_lines_json_all -- with
+        collapse_repeats through a json_all LineStream drained per batch, as _parse_collapsed does for 'json': its
+        state carries the run of repeats from batch to batch, so both values of ``stream`` publish the same texts."""
+        p = self.c.parser
+        if not self.collapse:
+            return p.parse_lines_json_all(lines, dispatch=self.rules, **self._profile_kw())
+        if self._stream is None:
+            kw = {} if times is None else {"repeat_window": self.window_us / 1e6}
+            if self.rules is not None:
+                kw["rules"] = self.rules
+            self._stream = p.stream(chunk_lines=self.max_batch, output="json_all", lag=1, collapse_repeats=True, **kw,
+                                    **self._profile_kw())
+        self._stream.submit(lines, **({} if times is None else {"times": times}))
+        return self._stream.drain()[0].texts_all()
+
     def _parse_routed(self, lines: List[Any]) -> List[Any]:
         kw = self._route_kw()
         return self.c.parser.parse_lines_routed(lines, kw.pop("routes"), **kw)
@@ -398,7 +435,7 @@ class BatchingParserTask:
                 batch = await self._next_batch()
                 lines = list(filter(None, batch))
                 if lines:
-                    parse = (self._parse_collapsed if self.collapse else
+                    parse = (self._parse_all if self.all else self._parse_collapsed if self.collapse else
                              self._parse_routed if self.routes is not None else
                              self._parse_profiled if self.profiles is not None else
                              c.parser.parse_lines_json if self.publish == "json" else c.parser.parse_lines)
@@ -412,6 +449,10 @@ class BatchingParserTask:
                         if self.publish == "json":
                             if res is not None and c.mqtt_publisher:
                                 await self._publish_json(res)
+                        elif self.all:
+                            if c.mqtt_publisher:
+                                for text in res or []:   # the line's texts in order
+                                    await self._publish_json(text)
                         else:
                             if res and c.message_callback:
                                 await c.message_callback(res[0])

@@ -221,12 +221,16 @@ JD void emit(S& o, const sdx_json_in& in, const BankView& bv, const sdx_json_rec
 
 constexpr int JT = 256;
 
-// The body of k_json / k_json_skip.  SKIP is a template argument, not a runtime pointer test: with the
-// pointer as an argument of the one kernel the unmasked JSON stream measured 0.6 % slower than before,
-// outside its run-to-run spread, so sdx_serialize_json keeps the kernel it had.
-template <bool SKIP>
+// The body of k_json / k_json_skip / k_json_lines.  SKIP is a template argument, not a runtime pointer test: with
+// the pointer as an argument of the one kernel the unmasked JSON stream measured 0.6 % slower than before,
+// outside its run-to-run spread, so sdx_serialize_json keeps the kernel it had.  LINES
+// (sdx_serialize_json_lines) is one for the same reason: lane = record of this kind, written at
+// its CHUNK record index first[msg] + (its place in its line's list), where all kinds of a chunk share off / len;
+// ``first`` and ``rec_cap`` (the capacity of off / len) are read in that instantiation only.
+template <bool SKIP, bool LINES = false>
 JD void json_body(const void* __restrict__ bank, const sdx_json_in& in, const sdx_json_out& out,
-                  const uint8_t* __restrict__ skip) {
+                  const uint8_t* __restrict__ skip, const uint32_t* __restrict__ first = nullptr,
+                  uint32_t rec_cap = 0) {
   const BankView bv = bank_view(bank);
   const sdx_bank_hdr* h = bv.hdr;
   const uint32_t cls0 = in.kind == SDX_KIND_MU ? 0u
@@ -236,11 +240,31 @@ JD void json_body(const void* __restrict__ bank, const sdx_json_in& in, const sd
   const sdx_json_rec* jt = reinterpret_cast<const sdx_json_rec*>(bv.base + h->off_json) + cls0;
   const int lane = threadIdx.x & 63;
   const int g = blockIdx.x * JT + threadIdx.x;
-  const int nitems = in.first_only ? in.n : min((int)in.cursor_dev[0], in.rec_max);
+  const int nitems = (!LINES && in.first_only) ? in.n : min((int)in.cursor_dev[0], in.rec_max);
   bool have = false;
   Item it{0, nullptr};
+  uint32_t slot = 0;  // LINES: where off / len are written
+  int idx_ovf = 0;
   if (g < nitems) {
-    if (in.first_only) {
+    if constexpr (LINES) {
+      // the record gets a text only where an OK descriptor covers it (not the stale records of an overflowed
+      // line) and the index gave its line the range (not a skipped line's)
+      const uint32_t m = in.rec_dev[g].msg;
+      if (m < (uint32_t)in.n) {
+        const sdx_desc d = in.desc_dev[m];
+        const uint32_t j = (uint32_t)g - d.rec_begin;  // g < rec_begin wraps: above every n_rec
+        const uint32_t f0 = first[m];
+        if (d.status == SDX_ST_OK && j < d.n_rec && j < first[m + 1] - f0) {
+          slot = f0 + j;
+          if (slot < rec_cap) {
+            have = true;
+            it = Item{(int)m, in.rec_dev + g};
+          } else {
+            idx_ovf = 1;  // the index does not fit off / len: nothing stored, the overflow flag
+          }
+        }
+      }
+    } else if (in.first_only) {
       const sdx_desc d = in.desc_dev[g];
       if (d.status == SDX_ST_OK && d.n_rec > 0) {
         have = true;
@@ -276,11 +300,19 @@ JD void json_body(const void* __restrict__ bank, const sdx_json_in& in, const sd
   }
   base = (uint32_t)__shfl((int)base, 0);
   ovf = __shfl(ovf, 0);
+  if constexpr (LINES) {
+    if (idx_ovf) atomicOr(&out.cursor_dev[1], 1u);
+  }
   if (g >= nitems) return;
-  if (in.first_only == 2 && !have) return;   // sparse: only the lines with a text (kinds share the outputs)
+  if ((LINES || in.first_only == 2) && !have) return;   // sparse: only the items with a text (kinds share the outputs)
   const uint32_t off = base + incl - len;
-  out.off_dev[g] = off;
-  out.len_dev[g] = ovf ? 0u : len;
+  if constexpr (LINES) {
+    out.off_dev[slot] = off;
+    out.len_dev[slot] = ovf ? 0u : len;
+  } else {
+    out.off_dev[g] = off;
+    out.len_dev[g] = ovf ? 0u : len;
+  }
   if (!have || ovf) return;
   J8 w(out.json_dev + off);
   emit(w, in, bv, jt, it);
@@ -294,6 +326,11 @@ __global__ __launch_bounds__(JT) void k_json(const void* __restrict__ bank, sdx_
 __global__ __launch_bounds__(JT) void k_json_skip(const void* __restrict__ bank, sdx_json_in in, sdx_json_out out,
                                                   const uint8_t* __restrict__ skip) {
   json_body<true>(bank, in, out, skip);
+}
+
+__global__ __launch_bounds__(JT) void k_json_lines(const void* __restrict__ bank, sdx_json_in in, sdx_json_out out,
+                                                   const uint32_t* __restrict__ first, uint32_t rec_cap) {
+  json_body<false, true>(bank, in, out, nullptr, first, rec_cap);
 }
 
 // ---- sdx_format_floats: lane = value, 32 bytes of output per lane as four aligned 8-byte stores
@@ -343,8 +380,8 @@ extern "C" int sdx_format_floats(const double* val_dev, int32_t n, int32_t json_
   return SDX_OK;
 }
 
-static int serialize_json(const sdx_bank* bank, const sdx_json_in* in, const sdx_json_out* out,
-                          const uint8_t* skip_dev, void* hip_stream) {
+// the argument checks of all three entries
+static int check_json_args(const sdx_bank* bank, const sdx_json_in* in, const sdx_json_out* out) {
   if (!bank || !in || !out) return sdx::set_error(SDX_EINVAL, "sdx_serialize_json: null argument");
   if (in->kind < SDX_KIND_MU || in->kind > SDX_KIND_MN)
     return sdx::set_error(SDX_EINVAL, "sdx_serialize_json: bad kind");
@@ -353,6 +390,12 @@ static int serialize_json(const sdx_bank* bank, const sdx_json_in* in, const sdx
     return sdx::set_error(SDX_EINVAL, "sdx_serialize_json: null buffer");
   if (in->kind == SDX_KIND_MS && (!in->pat_val_dev || !in->cp_slot_dev))
     return sdx::set_error(SDX_EINVAL, "sdx_serialize_json: MS needs pat_val/cp_slot");
+  return SDX_OK;
+}
+
+static int serialize_json(const sdx_bank* bank, const sdx_json_in* in, const sdx_json_out* out,
+                          const uint8_t* skip_dev, void* hip_stream) {
+  if (const int rc = check_json_args(bank, in, out)) return rc;
   const int items = in->first_only ? in->n : in->rec_max;
   if (items <= 0) return SDX_OK;
   if (skip_dev)
@@ -374,4 +417,20 @@ extern "C" int sdx_serialize_json(const sdx_bank* bank, const sdx_json_in* in, c
 extern "C" int sdx_serialize_json_skip(const sdx_bank* bank, const sdx_json_in* in, const sdx_json_out* out,
                                        const uint8_t* skip_dev, void* hip_stream) {
   return serialize_json(bank, in, out, skip_dev, hip_stream);
+}
+
+extern "C" int sdx_serialize_json_lines(const sdx_bank* bank, const sdx_json_in* in, const sdx_json_out* out,
+                                        const uint32_t* first_dev, uint32_t rec_max, void* hip_stream) {
+  if (const int rc = check_json_args(bank, in, out)) return rc;
+  if (in->first_only != 0) return sdx::set_error(SDX_EINVAL, "sdx_serialize_json_lines: first_only must be 0");
+  if (in->n < 0) return sdx::set_error(SDX_EINVAL, "sdx_serialize_json_lines: n < 0");
+  if (!first_dev || ((uintptr_t)first_dev & 3))
+    return sdx::set_error(SDX_EINVAL, "sdx_serialize_json_lines: first_dev null or not 4-byte aligned");
+  if (in->rec_max <= 0) return SDX_OK;
+  hipLaunchKernelGGL(sdxj::k_json_lines, dim3((in->rec_max + sdxj::JT - 1) / sdxj::JT), dim3(sdxj::JT), 0,
+                     (hipStream_t)hip_stream, sdx::bank_dev_ptr(bank), *in, *out, first_dev, rec_max);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess)
+    return sdx::set_error(SDX_EHIP, std::string("sdx_serialize_json_lines: ") + hipGetErrorString(e));
+  return SDX_OK;
 }

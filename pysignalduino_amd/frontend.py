@@ -595,7 +595,7 @@ class SignalParser:
     def stream(self, chunk_lines: int = 250_000, chunk_bytes: Optional[int] = None, output: str = "json",
                lag: int = 3, collapse_repeats: bool = False, repeat_window: Optional[float] = None,
                repeat_sources: Optional[int] = None, routes=None, drop_unrouted: bool = False,
-               route_match: str = "first", profiles=None):
+               route_match: str = "first", profiles=None, rules=None):
         """A pipelined LineStream over this parser (pysignalduino_amd/stream.py): chunks of raw lines
         in, the controller's JSON texts (or the wire form) out, the PCIe copies, parse, demodulation
         and serialisation of successive chunks overlapping; the same per-line results as
@@ -605,9 +605,13 @@ class SignalParser:
         parse_lines_routed: ChunkResult.route and items_routed(); None leaves the stream as it is.
         ``route_match="any"`` (with ``routes``): the line's first message that a route wants is the published
         one; ChunkResult.pick holds its index.  ``profiles``: receiver profiles, every
-        submit names its lines' source ids as with ``repeat_sources`` (stream.py)."""
+        submit names its lines' source ids as with ``repeat_sources`` (stream.py).  ``output="json_all"``: every
+        message of a line, as parse_lines_json_all (ChunkResult.texts_all / items_all), with
+        ``rules`` (None, True or a dispatch.DispatchRules) what that call takes as ``dispatch``."""
         from .stream import LineStream
         kw = {} if repeat_window is None else {"repeat_window": repeat_window}
+        if rules is not None:
+            kw["rules"] = rules
         if repeat_sources is not None:
             kw["repeat_sources"] = repeat_sources
         _check_route_match(route_match, routes)

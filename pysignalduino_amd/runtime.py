@@ -53,7 +53,8 @@ EXPORTED = ["sdx_abi_version", "sdx_last_error", "sdx_source_hash", "sdx_layout_
             "sdx_repeat_sources_scratch_bytes", "sdx_route_table_create", "sdx_route_table_destroy",
             "sdx_route_table_lds_routes", "sdx_route_lines", "sdx_route_records", "sdx_route_skip",
             "sdx_profile_table_create", "sdx_profile_table_destroy", "sdx_profile_check", "sdx_profile_scratch_bytes",
-            "sdx_filter_records", "sdx_dispatch_scratch_bytes", "sdx_dispatch_records"]
+            "sdx_filter_records", "sdx_dispatch_scratch_bytes", "sdx_dispatch_records", "sdx_index_scratch_bytes",
+            "sdx_index_records", "sdx_serialize_json_lines"]
 REPEAT_SOURCES_MAX = 4096   # SDX_REPEAT_SOURCES_MAX
 # sdx_repeat_source_entry (csrc/sdx_repeat_layout.h): a source's slot header after a chunk + its last result-bearing line
 REPEAT_SOURCE_ENTRY = np.dtype([("valid", "<u4"), ("kind", "<u4"), ("proto", "<u4"), ("len", "<u4"), ("t", "<i8"),
@@ -314,6 +315,12 @@ def load_library(path: Optional[str] = None):
     lib.sdx_dispatch_records.argtypes = [c_void_p, POINTER(SdxDispatchRules), POINTER(SdxJsonIn), c_int, c_int32, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.sdx_dispatch_records.restype = c_int
+    lib.sdx_index_scratch_bytes.argtypes = [c_int32]
+    lib.sdx_index_scratch_bytes.restype = c_size_t
+    lib.sdx_index_records.argtypes = [POINTER(SdxJsonIn), c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.sdx_index_records.restype = c_int
+    lib.sdx_serialize_json_lines.argtypes = [c_void_p, POINTER(SdxJsonIn), POINTER(SdxJsonOut), c_void_p, c_uint32, c_void_p]
+    lib.sdx_serialize_json_lines.restype = c_int
     lib.sdx_parse_lines.argtypes = [POINTER(SdxLines), POINTER(SdxLinesOut), c_void_p]
     lib.sdx_parse_lines.restype = c_int
     lib.sdx_select_lines.argtypes = [POINTER(SdxLinesOut), c_int32, c_void_p, c_void_p, c_void_p, c_void_p]
@@ -1104,6 +1111,44 @@ class Engine:
         this pass reads payloads.  The heaps themselves stay as they are (payload offsets are unchanged)."""
         return self._fetched(res, n, True, self.alloc_dispatch,
                              lambda ins, bufs: self.dispatch_records(rules, ins, n, bufs))
+
+    # -- every message of a line in one chunk result (sdx_index_records, DESIGN.md §4p) ------------
+    def alloc_line_index(self, n: int, rec_max: int, json_cap: Optional[int] = None):
+        """The buffers of index_records + launch_json_lines for chunks of up to n lines and ``rec_max`` records over
+        all kinds: {"first": int32[n + 1] (uint32 values), "scratch", and alloc_json's "json" / "off" / "len" /
+        "cursor" / "cap" with off / len holding ``rec_max`` entries, "rec_max"}.  ``json_cap``: the text buffer's
+        bytes (default 256 per record + 64 KB)."""
+        t, d, n, rec_max = self.torch, self.dev, max(int(n), 0), max(int(rec_max), 0)
+        idx = self.alloc_json(rec_max, 256 * rec_max + 65536 if json_cap is None else int(json_cap))
+        # empty, not zeros: index_records writes every entry of first[0, n], and a fill would run on another stream
+        idx.update(first=t.empty(n + 1, dtype=t.int32, device=d), rec_max=rec_max, n=n,
+                   scratch=t.empty(int(self.lib.sdx_index_scratch_bytes(n)), dtype=t.uint8, device=d))
+        return idx
+
+    def index_records(self, json_ins, n: int, idx, skip=None, stream=None) -> None:
+        """sdx_index_records on ``stream`` (default: the current one; no host sync): idx["first"][: n + 1] = the
+        exclusive prefix, in line order, of every line's record count over ``json_ins`` (json_in, one per kind);
+        ``skip``: a device uint8[n] mask (mark_repeats'), a line with a non-zero entry counts 0."""
+        n = int(n)
+        if not 1 <= len(json_ins) <= 4:
+            raise ValueError("index_records: 1 to 4 kinds")
+        if n > idx["n"] or (skip is not None and skip.numel() * skip.element_size() < n):
+            raise ValueError("index_records: a buffer is too small for n")
+        arr = (SdxJsonIn * len(json_ins))(*json_ins)
+        st = self.stream_ptr() if stream is None else c_void_p(stream.cuda_stream)
+        _check(self.lib, self.lib.sdx_index_records(arr, len(json_ins), n, _ptr(skip), _ptr(idx["first"]),
+                                                    _ptr(idx["scratch"]), st))
+
+    def launch_json_lines(self, kind: int, demod_out, lines_out, n: int, idx) -> None:
+        """sdx_serialize_json_lines over a demodulation launch's device outputs (no host sync): one text per record
+        of the lines index_records counted, its offset and length at the record's chunk index in idx["off"] /
+        idx["len"] (alloc_line_index's; the caller zeroes idx["cursor"] once per chunk, all kinds share it)."""
+        if n > idx["n"]:
+            raise ValueError("launch_json_lines: the index holds fewer than n lines")
+        ji = self.json_in(kind, demod_out, lines_out, n, 0)
+        jo = SdxJsonOut(_ptr(idx["json"]), _ptr(idx["off"]), _ptr(idx["len"]), _ptr(idx["cursor"]), idx["cap"], 0)
+        _check(self.lib, self.lib.sdx_serialize_json_lines(self.handle, ctypes.byref(ji), ctypes.byref(jo),
+                                                           _ptr(idx["first"]), idx["rec_max"], self.stream_ptr()))
 
     def alloc_json(self, items: int, cap: int):
         t, d = self.torch, self.dev

@@ -160,6 +160,10 @@ class ChunkResult:
         self.id, self.n, self.kind, self.status = cid, n, kind, status
         self.slot = None          # the _Slot whose pinned buffers the arrays view (None once detached)
         self.json = self.off = self.len = None
+        # json_all output: uint32[n + 1], line i's records are [first[i], first[i + 1]) of off / len,
+        # which are then indexed by record; host[i] holds a list of texts
+        self.first = None
+        self.overflow = False     # json_all: the chunk's texts or index overflowed, every decoding line came from the host
         self.wire = self.layout = None
         self.host = {}            # line -> result of the batch API (fallback lines)
         self.repeat = None        # collapse_repeats: uint8[n], 1 = the line repeats the previous result-bearing one
@@ -193,7 +197,7 @@ class ChunkResult:
         self.slot = None
         if isinstance(self.src_data, _ChunkBytes):   # views of the slot's or the caller's pinned memory
             self.src_data, self.src_offsets = self.src_data.copy(), self.src_offsets.copy()
-        for f in ("kind", "status", "off", "len", "wire", "repeat", "route", "pick"):
+        for f in ("kind", "status", "off", "len", "first", "wire", "repeat", "route", "pick"):
             v = getattr(self, f)
             if isinstance(v, np.ndarray):
                 setattr(self, f, v.copy())
@@ -210,6 +214,8 @@ class ChunkResult:
     def items(self) -> List[Tuple[int, Union[str, Exception]]]:
         """(line, text or ContractError) for the lines that publish something, in line order: the
         sparse form of texts() (one ASCII decode of the chunk's text buffer, one slice per text)."""
+        if self.first is not None:
+            raise ValueError("a json_all chunk: texts_all() / items_all()")
         rows = np.nonzero(self.len)[0]
         blob = bytes(self.json).decode("ascii")
         dev = zip(rows.tolist(), [blob[o: o + ln] for o, ln in zip(self.off[rows].tolist(), self.len[rows].tolist())])
@@ -218,6 +224,36 @@ class ChunkResult:
         d = dict(dev)
         d.update(self.host)
         return [(i, d[i]) for i in sorted(d) if d[i] is not None]
+
+    def texts_all(self) -> List[Union[List[str], Exception]]:
+        """A json_all chunk: per line the MQTT texts of every message it publishes, in order
+        (``parse_lines_json_all``'s slot): [] where nothing is published, the line's ContractError in its slot."""
+        out: List[Any] = [[] for _ in range(self.n)]
+        for i, r in self.items_all():
+            out[i] = r
+        return out
+
+    def items_all(self) -> List[Tuple[int, Union[List[str], Exception]]]:
+        """(line, its list of texts or its ContractError) for the lines with at least one text or an exception, in
+        line order: one ASCII decode of the chunk's text buffer, one slice per text.  A record of length 0 is no
+        text."""
+        if self.first is None:
+            raise ValueError("no json_all chunk: texts() / items()")
+        first = self.first.astype(np.int64)
+        total = int(first[self.n])
+        ln = self.len[:total]
+        recs = np.nonzero(ln)[0]
+        blob = bytes(self.json).decode("ascii")
+        texts = [blob[o: o + k] for o, k in zip(self.off[:total][recs].tolist(), ln[recs].tolist())]
+        lines = (np.searchsorted(first, recs, side="right") - 1).tolist()   # first is non-decreasing
+        d: dict = {}
+        for i, x in zip(lines, texts):
+            if i not in self.host:
+                d.setdefault(i, []).append(x)
+        for i, x in self.host.items():
+            if isinstance(x, BaseException) or x:
+                d[i] = x
+        return [(i, d[i]) for i in sorted(d)]
 
     def items_routed(self) -> List[Tuple[int, int, Union[str, Exception]]]:
         """items() with every line's route: (line, route, text or ContractError), route -1 = unrouted (a
@@ -282,6 +318,14 @@ class _Slot:
             self.jout = eng.alloc_json(C, self.jcap)
             self.h_sizes = t.zeros(2 + 4 * len(self.outs), dtype=t.int32).pin_memory()
             self.h_out = t.empty(self.jcap + 11 * C + 64, dtype=t.uint8).pin_memory()
+        elif ls.all:
+            # every message of a line: one record-indexed result for all kinds.  The index cannot
+            # overflow (no pass adds records); the text buffer is twice the json stream's, the one-shot call's first try
+            self.rec_max = sum(o["rec_cap"] for o in self.outs.values())
+            self.jcap = 2 * (600 * C + 65536)
+            self.idx = eng.alloc_line_index(C, self.rec_max, self.jcap)
+            self.h_sizes = t.zeros(3 + 4 * len(self.outs), dtype=t.int32).pin_memory()   # text cursor [2], first[n], cursors
+            self.h_out = t.empty(self.jcap + 4 * (C + 1) + 8 * self.rec_max + 3 * C + 64, dtype=t.uint8).pin_memory()
         else:
             from . import dist as sdist
             self.ser = sdist.Exchange.sender(eng)
@@ -299,6 +343,10 @@ class _Slot:
             if ls.n_sources is None and ls.profiles.n_sources > 1:
                 self.p_d_src = t.zeros(C, dtype=t.int32, device=eng.dev)
                 self.p_h_src = t.zeros(C, dtype=t.int32).pin_memory()
+        if ls.rules is not None:
+            # the dispatch pass's outputs, behind the profile pass's where there is one
+            self.dp = eng.alloc_dispatch(C, list((self.fouts if ls.profiles is not None else self.outs).values()))
+            self.douts = dict(zip(self.outs, self.dp["outs"]))
         if ls.routes is not None:   # the route pass's outputs; its skip mask only where the device drops the unrouted
             extra = {"pick": True, "views": len(self.outs)} if ls.match_any else {}   # "first": the call as it was
             self.rt = eng.alloc_routes(C, mask=False, skip=ls.device_drop, **extra)
@@ -336,6 +384,11 @@ class LineStream:
     routed lines only (a wire stream's sections are never changed).  ``route_match="any"``: the
     line's first message that a route matches is the published one -- the match runs first (sdx_route_records), the
     repeat pass and the serialiser over its picked views; ChunkResult.pick holds the message's index.
+    ``output="json_all"``: every message of a line, as ``parse_lines_json_all`` -- the chunk's texts
+    are indexed by record, ChunkResult.first gives every line its range, texts_all() / items_all() the lists;
+    ``rules`` (None: every message; True or a dispatch.DispatchRules: FHEM's dispatch rules) reduces
+    every list on the device first.  It combines with ``profiles`` and repeat suppression (a repeat line gives []),
+    not with routes.
 
     submit(lines) -> chunk id; ``submit_packed(data, offsets)`` the same for lines already packed as
     (uint8 bytes, int64 offsets[n + 1]); ``submit_bytes(buf)`` -> chunk ids for a transport's raw read
@@ -346,12 +399,21 @@ class LineStream:
     def __init__(self, parser, chunk_lines: int = 250_000, chunk_bytes: Optional[int] = None, output: str = "json",
                  lag: int = 3, collapse_repeats: bool = False, repeat_window: Optional[float] = None,
                  repeat_sources: Optional[int] = None, routes=None, drop_unrouted: bool = False,
-                 route_match: str = "first", profiles=None):
-        if output not in ("json", "wire"):
-            raise ValueError("output must be 'json' or 'wire'")
+                 route_match: str = "first", profiles=None, rules=None):
+        if output not in ("json", "wire", "json_all"):
+            raise ValueError("output must be 'json', 'json_all' or 'wire'")
+        # every message of a line: ``rules``, not ``dispatch`` -- the name the one-shot calls use is
+        # pinned to raise TypeError on a stream
+        self.all = output == "json_all"
+        from .dispatch import as_rules
+        self.rules = as_rules(rules)            # dispatch rules; None: every message, no pass, no buffer
+        if self.rules is not None and not self.all:
+            raise ValueError("rules need output='json_all'")
+        if self.all and (routes is not None or drop_unrouted or route_match != "first"):
+            raise ValueError("output='json_all' takes no routes (routes per record are not covered)")
         from .profiles import as_profiles
         self.profiles = as_profiles(profiles)   # receiver profiles; None: no pass, no buffer
-        if self.profiles is not None and output != "json":
+        if self.profiles is not None and output == "wire":
             # the exchange pack reads the demodulation kernels' own per-message counts, which the pass does not rewrite
             raise ValueError("profiles need output='json'")
         from .frontend import _check_route_match
@@ -384,6 +446,8 @@ class LineStream:
         self.parser = parser
         self.eng = parser.protocols._ensure()
         self.bank = parser.protocols._bank
+        if self.rules is not None:
+            self.drules = self.rules.struct(self.bank)   # compiled once; an id the bank does not know raises here
         self.mc = parser.protocols.mc_mode == "fixed"   # 'strict' MC reaches no device launch
         self.output = output
         self.C = int(chunk_lines)
@@ -707,7 +771,9 @@ class LineStream:
         cl, m = len(carry), hi - lo
         nb = cl + m
         if not hasattr(s, "d_split"):   # the split's buffers, on the slot's first byte chunk
-            s.d_split = t.zeros(2, dtype=t.int64, device=self.eng.dev)
+            # empty, not zeros: a fill kernel would run on the framework's stream, unordered against the split below,
+            # which writes both words
+            s.d_split = t.empty(2, dtype=t.int64, device=self.eng.dev)
             s.h_split = t.zeros(2, dtype=t.int64).pin_memory()
             s.split_scratch = t.empty(self.eng.split_work_ints(self.B), dtype=t.int32, device=self.eng.dev)
         hb = s.h_bytes.numpy()
@@ -820,6 +886,14 @@ class LineStream:
                 d_src = None if s.sources is None else s.rb.d_src if self.n_sources is not None else s.p_d_src
                 eng.filter_records(self.ptable, ins, n, s.pf, source=d_src, stream=sd)
                 outs = s.fouts
+            if self.rules is not None:
+                # the dispatch rules behind the profiles: a disabled protocol never counts.  A line's
+                # first record stays, so the repeat pass below decides what a json stream's would
+                ins = [eng.json_in(kd, outs[name], lo, n, 2) for name, kd, _, _ in _KINDS if name in outs]
+                for o in s.dp["outs"]:
+                    o["n"] = n
+                eng.dispatch_records(self.drules, ins, n, s.dp, stream=sd)
+                outs = s.douts
             if self.match_any:
                 # every line's published record and the views in which it owns exactly that one;
                 # nothing of this waits for the previous chunk
@@ -859,6 +933,20 @@ class LineStream:
                         eng.launch_json(kd, o, lo, n, jo, first_only=2, **skip)
                 runtime.copy_async(s.h_sizes[:2], jo["cursor"], sd)
                 runtime.copy_async(s.h_sizes[2:], s.cursors.reshape(-1), sd)
+            elif self.all:
+                # the chunk's line -> record-range index over all kinds (a repeat line counts 0), then one text per
+                # record at its chunk index: one off / len / text buffer for the chunk
+                ix = s.idx
+                ins = [eng.json_in(kd, outs[name], lo, n, 0) for name, kd, _, _ in _KINDS if name in outs]
+                eng.index_records(ins, n, ix, skip=s.rep if self.collapse else None, stream=sd)
+                runtime.fill_async(ix["cursor"], sd)
+                for name, kd, short, long_ in _KINDS:
+                    o = outs.get(name)
+                    if o is not None and (cnt[short] or (long_ is not None and cnt[long_])):
+                        eng.launch_json_lines(kd, o, lo, n, ix)
+                runtime.copy_async(s.h_sizes[:2], ix["cursor"], sd)
+                runtime.copy_async(s.h_sizes[2:3], ix["first"][n: n + 1], sd)
+                runtime.copy_async(s.h_sizes[3:], s.cursors.reshape(-1), sd)
             else:
                 from . import dist as sdist
                 parts = [sdist.Part(o["desc"], o["rec"], o["heap"], n, o["cursor"], kd, wire=o.get("wire"),
@@ -898,6 +986,22 @@ class LineStream:
                 runtime.copy_async(ho[a + 4 * n: a + 8 * n], s.jout["len"][:n], self.cout)
                 b = a + 8 * n
                 s.lay = (T, a)
+            elif self.all:
+                # the texts, first[: n + 1] and off / len[: total] -- record-indexed, all kinds' -- in the same sized copy
+                T = int(min(hs[0], s.jcap))
+                R = int(min(max(hs[2], 0), s.rec_max))
+                s.ovf_json = bool(hs[1])
+                s.dcur = hs[3:].reshape(k, 4)
+                ix = s.idx
+                runtime.copy_d2h(ho[:T], ix["json"][:T], self.cout)
+                a = (T + 3) & ~3
+                runtime.copy_async(ho[a: a + 4 * (n + 1)], ix["first"][: n + 1], self.cout)
+                a2 = a + 4 * (n + 1)
+                if R:
+                    runtime.copy_async(ho[a2: a2 + 4 * R], ix["off"][:R], self.cout)
+                    runtime.copy_async(ho[a2 + 4 * R: a2 + 8 * R], ix["len"][:R], self.cout)
+                b = a2 + 8 * R
+                s.lay = (T, a, R)
             else:
                 from . import dist as sdist
                 S = hs[: runtime.XCHG_COUNTS * k].reshape(1, k, runtime.XCHG_COUNTS)
@@ -950,6 +1054,16 @@ class LineStream:
             r.len = ho[a + 4 * n: a + 8 * n].view(np.uint32)
             if s.ovf_json:
                 redo_kinds = set(names)            # the text buffer overflowed: the batch API for all
+        elif self.all:
+            T, a, R = s.lay
+            a2 = a + 4 * (n + 1)
+            r.json = memoryview(ho[:T])
+            r.first = ho[a: a2].view(np.uint32)
+            r.off = ho[a2: a2 + 4 * R].view(np.uint32)
+            r.len = ho[a2 + 4 * R: a2 + 8 * R].view(np.uint32)
+            r.overflow = s.ovf_json
+            if s.ovf_json:
+                redo_kinds = set(names)            # the texts or the index overflowed: the batch API for all
         else:
             r.wire = ho[: s.lay[2]]
             r.layout = s.lay
@@ -975,6 +1089,8 @@ class LineStream:
                 res = [x[1] if isinstance(x, tuple) else x
                        for x in self.parser.parse_lines_routed(lines, self.routes, route_match="any", **pkw)]
                 host_picks = dict(zip(rows, zip(self.parser.last_picks.tolist(), self.parser.last_routes.tolist())))
+            elif self.all:   # every message's text, through the same passes on the host-resolved lines alone
+                res = self.parser.parse_lines_json_all(lines, dispatch=self.rules, **pkw)
             else:
                 res = (self.parser.parse_lines_json(lines, **pkw) if self.output == "json" else self.parser.parse_lines(lines))
             for i, x in zip(rows, res):
@@ -1025,10 +1141,13 @@ class LineStream:
         """r.repeat = the chunk's exact mask: the device's, re-decided around the host-resolved rows
         (repeats.RepeatTracker); texts and host results follow it."""
         from .repeats import apply_mask, objects_key, text_key
-        n, kind, js = r.n, r.kind, self.output == "json"
+        n, kind, js, al = r.n, r.kind, self.output == "json", self.all
         name_of = lambda i: kname.get(int(kind[i]), "?")   # noqa: E731
         picked = lambda i, x: x[int(r.pick[i]): int(r.pick[i]) + 1] if r.pick is not None and isinstance(x, list) else x   # noqa: E731
-        host_keys = {i: ((text_key(name_of(i), x) if isinstance(x, str) else None) if js else objects_key(picked(i, x)))
+        # json_all: a line's key is that of its first text, which the dispatch rules never remove
+        list_key = lambda i, x: text_key(name_of(i), x[0]) if isinstance(x, list) and x else None   # noqa: E731
+        host_keys = {i: (list_key(i, x) if al else (text_key(name_of(i), x) if isinstance(x, str) else None) if js
+                         else objects_key(picked(i, x)))
                      for i, x in r.host.items()}
         redo = [i for i in r.host if redo_kinds and kname.get(int(kind[i])) in redo_kinds
                 and r.status[i] == runtime.LS_OK]
@@ -1036,6 +1155,8 @@ class LineStream:
 
         def one_text(i):       # the line's published text on its own (route_match="any": the picked message's)
             pkw = self._profile_args(s, [i])
+            if al:             # json_all: the line's list
+                return self.parser.parse_lines_json_all([self._line(s, i)], dispatch=self.rules, **pkw)[0]
             if not self.match_any:
                 return self.parser.parse_lines_json([self._line(s, i)], **pkw)[0]
             x = self.parser.parse_lines_routed([self._line(s, i)], self.routes, route_match="any", **pkw)[0]
@@ -1043,9 +1164,20 @@ class LineStream:
 
         def fetch(i):
             fetched[i] = one_text(i)
+            if al:
+                return list_key(i, fetched[i])
             return text_key(name_of(i), fetched[i]) if isinstance(fetched[i], str) else None
 
-        if js:
+        if al:
+            first = r.first.astype(np.int64)
+            has_key = np.diff(first) > 0     # a repeat the device skipped has no range, as it has no text in a json chunk
+            blob = r.json
+
+            def dev_key_of(i):
+                c = int(first[i])
+                o = int(r.off[c])
+                return text_key(name_of(i), bytes(blob[o: o + int(r.len[c])]).decode("ascii"))
+        elif js:
             has_key = r.len > 0
             blob = r.json
 
@@ -1056,12 +1188,14 @@ class LineStream:
             has_key, dev_key_of = self._wire_keys(r)
         r.repeat = mask = self.repeats.exact_mask(s.rb, rep, has_key, dev_key_of, host_keys, redo, fetch,
                                                   times=s.times, sources=self._rsrc(r.source), bank=self.bank)
-        if not js:
+        if not (js or al):
             return
 
         def drop(i):
             if i in r.host:
-                r.host[i] = None
+                r.host[i] = [] if al else None
+            elif al:
+                r.len[int(first[i]): int(first[i + 1])] = 0   # every record of the line
             else:
                 r.len[i] = 0           # a repeat of a host-resolved line: its text is not published
 
